@@ -8,9 +8,16 @@ Batch is sharded across ranks (one process per GPU, weak scaling, no data-path c
 SURVEY.md section 8e "inference").
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0.  `roofline` is for the kernel instantiation with the largest
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`); everything else below -- the repeats, `roofline` / `kernels`, the sustained 608 keys, the other-precision
+paths, the training key and `cpu_baseline` -- runs only under --full (each still switched off by its --no-* flag there).
+--dump-outputs DIR writes what the timed step returned in its last step as DIR/<name>.npy (see dump_outputs).
+
+`roofline` is for the kernel instantiation with the largest
 total time: achieved = algorithmic conv FLOPs of its launches / their HIP-event durations,
 measured live in a second pass over the same K steps (events bracket each launch on the stream the
 kernels run on; the headline `value` pass itself carries no events).  `cpu_baseline` times the
@@ -331,9 +338,10 @@ def synthetic_labels(batch, seed, num_class=24):
     return lab
 
 
-def train_pass(args, spec, size, B, rank, world, dev, dist, steps, warmup, preheat_s=0.0, telemetry=None):
+def train_pass(args, spec, size, B, rank, world, dev, dist, steps, warmup, preheat_s=0.0, telemetry=None, dump_dir=None):
     """BASELINE configs[2] (N=1) / configs[3] (N>1): car/YOLO.py training step, B images per GPU, the gradient
-    bucket all-reduced over RCCL (one exchange per step), identical Adam on every rank.  Returns the result dict."""
+    bucket all-reduced over RCCL (one exchange per step), identical Adam on every rank.  dump_dir: rank 0 writes the last
+    timed step's losses there (--dump-outputs).  Returns the result dict."""
     from yolo_amd.net import CarNet
     from yolo_amd.train import Trainer
     from yolo_amd import parallel
@@ -384,6 +392,8 @@ def train_pass(args, spec, size, B, rank, world, dev, dist, steps, warmup, prehe
     fence()
     el = time.perf_counter() - t0
     tinfo = telemetry.stop() if telemetry is not None else {}
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, {'losses': losses})
     per_rank = [el]
     if dist is not None:
         t = torch.zeros(world, device=dev, dtype=torch.float64)
@@ -499,7 +509,7 @@ def plan_report(args, state):
 
 
 def bench_train(args, spec, size, B, rank, world, dev, dist):
-    out = train_pass(args, spec, size, B, rank, world, dev, dist, args.steps, args.warmup)
+    out = train_pass(args, spec, size, B, rank, world, dev, dist, args.steps, args.warmup, dump_dir=args.dump_outputs)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
@@ -517,12 +527,16 @@ def _free_port():
 
 
 def relaunch_under_torchrun(n, argv):
-    """`python bench.py --gpus N` without a launcher: start N ranks on this node (one process per GPU) and hand the
-    job over to them -- the command line the driver uses for N > 1."""
+    """`python bench.py --gpus N` without a launcher: start N ranks on this node (one process per GPU) under a launcher in
+    a child process and exit with its status -- the command line the driver uses for N > 1.  (A child, not exec: this
+    process has already asked the runtime how many GPUs there are, and a process that holds the GPU must not replace
+    itself with another program.)"""
+    import subprocess
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(n),
            '--master-addr', '127.0.0.1', '--master-port', str(_free_port()), os.path.abspath(__file__)] + list(argv)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get('HSA_ENABLE_IPC_MODE_LEGACY', '0'))
-    os.execvpe(cmd[0], cmd, env)
+    sys.stdout.flush()
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 def launch_check(backend, rank, world, local):
@@ -560,12 +574,49 @@ def emit(out):
     print(json.dumps(out), flush=True)
 
 
-def timed_pass(net, det, x, post, steps, warmup, fence, preheat_s=0.0, telemetry=None):
+DUMP_BYTES = 64 * 10 ** 6                 # --dump-outputs: at most this many bytes in all
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BYTES, seed=0):
+    """--dump-outputs: {name: array or tensor} -> outdir/<name>.npy, float64 for integer arrays (exact) and float64 data,
+    float32 for everything else, so that two builds can be compared output for output.  An array larger than its share of
+    `budget` is written as a fixed, seeded sample of its flattened elements (the same indices on every run with the same
+    arguments).  -> {name: {'shape': original shape, 'sampled': element count written or None}}"""
+    os.makedirs(outdir, exist_ok=True)
+    share = budget // max(len(arrays), 1) - 4096                     # (room for each file's .npy header)
+    report = {}
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach()
+            a = (a.float() if a.is_floating_point() and a.dtype != torch.float64 else a).cpu().numpy()
+        a = np.asarray(a)
+        a = a.astype(np.float64 if (a.dtype.kind in 'iub' or a.dtype == np.float64) else np.float32)
+        shape, sampled = list(a.shape), None
+        if a.nbytes > share:
+            k = share // a.itemsize
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, k, replace=False))
+            a, sampled = a.reshape(-1)[idx], int(k)
+        np.save(os.path.join(outdir, name + '.npy'), np.ascontiguousarray(a))
+        report[name] = {'shape': shape, 'sampled': sampled}
+    return report
+
+
+def step_outputs(post, res):
+    """What one timed step of `post` hands its caller, by name (dump_outputs)."""
+    if post == 'none':
+        return {'logits_%d' % i: o for i, o in enumerate(res)}          # (fine -> coarse; views of the plan's buffer)
+    if post == 'nms':
+        return dict(zip(('kept', 'kept_scores', 'kept_count'), res))
+    return {'rows': res}                                                 # (B, 6+C) rows of the reference's predict, on the host
+
+
+def timed_pass(net, det, x, post, steps, warmup, fence, preheat_s=0.0, telemetry=None, last=None):
     """W untimed + K timed steps of forward + post-processing; returns (seconds for the K steps on this rank, telemetry dict).
     post: 'none' forward only | 'top1' decode + per-image arg-max + the (B, 6+C) rows copied to the host (the reference's
     predict owns its D2H, car/YOLO.py:597; pipelined two deep: no host stall) | 'top1_blocking' the same with a blocking
     .cpu() per step | 'nms' decode + per-class NMS (kept ids stay on the device).  preheat_s: run the same step for that
-    many seconds first (clock / power state of a sustained run), outside the timed region."""
+    many seconds first (clock / power state of a sustained run), outside the timed region.  last: a list that receives what
+    the last timed step returned."""
     pend = [None]
 
     def step(i=0):
@@ -576,9 +627,9 @@ def timed_pass(net, det, x, post, steps, warmup, fence, preheat_s=0.0, telemetry
             if os.environ.get('YOLO_BENCH_NMS_TWO_CALLS'):          # (A/B knob: yolo_decode_scores + yolo_nms_from_scores)
                 rows, scores = det.decode_scores(outs, mode='class')
                 kept, ks, cnt = det.nms(rows, mode='class', scores=scores)
-                return kept, cnt
+                return kept, ks, cnt
             rows, scores, kept, ks, cnt = det.decode_nms(outs, mode='class')
-            return kept, cnt
+            return kept, ks, cnt
         if post == 'top1_blocking':
             return det.predict(outs)
         host, ev = det.predict_async(outs, slot=i & 1)
@@ -600,9 +651,11 @@ def timed_pass(net, det, x, post, steps, warmup, fence, preheat_s=0.0, telemetry
         telemetry.start()
     t0 = time.perf_counter()
     for i in range(steps):
-        step(i)
+        res = step(i)
     fence()
     el = time.perf_counter() - t0
+    if last is not None:
+        last.append(res)
     return el, (telemetry.stop() if telemetry is not None else {})
 
 
@@ -654,7 +707,18 @@ def main():
     ap.add_argument('--grad-buckets', type=int, default=4, help='N > 1 training: number of buckets the 492 MB gradient buffer is cut into')
     ap.add_argument('--launch-check', action='store_true',
                     help='start the N ranks, rendezvous, barrier, MAX-reduce, print the world that ran, and exit (no benchmark)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beyond the headline figure: the repeats, roofline / per-kernel times, the sustained 608 '
+                         'keys, the fp32 / split / f16 paths, the training key and the CPU baseline (each still off under its --no-* '
+                         'flag).  Without it a run only sets up, warms up, times --steps steps and prints the line')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the timed step returned in its last step as DIR/<name>.npy (float32 / '
+                         'float64, at most 64 MB in all: a larger output is a fixed, seeded sample of its elements; rank 0 only)')
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit('--steps must be >= 1')
+    if not args.full:
+        args.no_repeats = args.no_roofline = args.no_northstar = args.no_f32_key = args.no_train_key = args.no_cpu_baseline = True
 
     backend = os.environ.get('YOLO_BENCH_BACKEND', 'nccl')          # ('gloo': the CPU test of the launcher path)
     need_gpu = not (args.launch_check and backend == 'gloo')
@@ -753,7 +817,11 @@ def main():
     # `value` times the reference's LITERAL predict (car/YOLO.py:568-597): the rows are copied to the host by a blocking copy in
     # every step, as rounds 1-3 measured it; the pipelined copy (pinned buffers, two deep) is `value_async_predict`
     post_main = 'top1_blocking' if args.post == 'top1' else args.post
-    el, per_rank = over_ranks(timed_pass(net, det, x, post_main, args.steps, args.warmup + setup_steps, fence)[0])
+    last = []
+    el, per_rank = over_ranks(timed_pass(net, det, x, post_main, args.steps, args.warmup + setup_steps, fence, last=last)[0])
+    if args.dump_outputs and rank == 0:                  # (now: the 'none' step's logits are views the next forward overwrites)
+        dump_outputs(args.dump_outputs, step_outputs(post_main, last[0]))
+    del last
     ms_per_step = el / args.steps * 1e3
     value = world * B * args.steps / el
     # the same K-step pass four more times: `value` stays the first pass (what the driver's clock brackets), the median of

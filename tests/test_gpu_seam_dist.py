@@ -394,7 +394,7 @@ def test_bench_two_ranks_sharing_the_gpu(world):
     import gc
     gc.collect()
     torch.cuda.empty_cache()                # (the N ranks share THIS process's GPU: give back what the earlier tests cached)
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(world), '--steps', '3', '--warmup', '1', '--no-northstar',
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(world), '--steps', '3', '--warmup', '1', '--full', '--no-northstar',
                         '--no-roofline', '--no-repeats', '--sustain-steps', '0', '--train-timeout', '900'], env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -425,7 +425,7 @@ def test_bench_line_launches_the_committed_plan_and_quotes_its_own_pmc_pass():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '1', '--no-northstar', '--no-train-key',
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '1', '--full', '--no-northstar', '--no-train-key',
                         '--no-f32-key', '--no-cpu-baseline', '--no-repeats'], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
@@ -434,3 +434,29 @@ def test_bench_line_launches_the_committed_plan_and_quotes_its_own_pmc_pass():
     assert rf['traffic'] is not None and rf['traffic_source'].startswith('profiles/'), rf
     assert rf['traffic'] >= 0.9 * rf['algorithmic_bytes'] and 0.2 < rf['frac'] < 1.0
     assert d['dtype'] == 'bf16' and d['config']['global_batch'] == 32 and d['unit'] == 'images/s'
+
+
+def test_plain_bench_run_is_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """`bench.py --steps K --warmup W` without --full: the K timed steps and the headline fields, none of the extras; with
+    --dump-outputs the last step's (B, 6+C) predict rows land as rows.npy in float32."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    out = str(tmp_path / 'outs')
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--dump-outputs', out],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in d, k
+    assert d['steps'] == 3 and d['dtype'] == 'bf16' and d['unit'] == 'images/s' and d['higher_is_better'] is True
+    assert abs(d['value'] * d['ms_per_step'] / 1e3 - 32) < 0.05
+    for k in ('roofline', 'kernels', 'northstar_608', 'f32_path', 'parity_path', 'f16_path', 'train_416_bs64', 'cpu_baseline',
+              'value_async_predict'):
+        assert k not in d, k
+    assert len(d['value_repeats']) == 1                                               # (one timed pass)
+    rows = np.load(os.path.join(out, 'rows.npy'))
+    assert rows.dtype == np.float32 and rows.ndim == 2 and rows.shape[0] == 32 and np.all(np.isfinite(rows))
+    assert np.all((rows[:, 0] >= 0) & (rows[:, 0] <= 1))                             # column 0: the top-1 box's score

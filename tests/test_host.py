@@ -132,6 +132,31 @@ def test_committed_bench_line_follows_the_contract():
     assert abs(d['value'] - d['n_gpus'] * d['config']['global_batch'] / d['n_gpus'] / (d['ms_per_step'] / 1e3)) / d['value'] < 0.01
 
 
+def test_bench_dump_outputs_writes_floats_and_a_fixed_sample_within_the_budget(tmp_path):
+    """bench.py --dump-outputs: every array lands as <name>.npy in float32 / float64 (integers exactly, in float64); an array over
+    its share of the byte budget is written as a seeded sample -- the same elements on every call -- and the files stay within it."""
+    import torch
+    import bench
+    big = np.arange(50000, dtype=np.float32).reshape(100, 500)
+    arrays = {'rows': big, 'kept': torch.tensor([[3, -1], [7, 2]], dtype=torch.int32), 'half': torch.ones(4, dtype=torch.bfloat16)}
+    budget = 3 * (4096 + 40000)
+    rep = bench.dump_outputs(str(tmp_path / 'a'), arrays, budget=budget)
+    bench.dump_outputs(str(tmp_path / 'b'), arrays, budget=budget)
+    assert rep == {'rows': {'shape': [100, 500], 'sampled': 10000}, 'kept': {'shape': [2, 2], 'sampled': None},
+                   'half': {'shape': [4], 'sampled': None}}
+    total = 0
+    for name in arrays:
+        a, b = np.load(str(tmp_path / 'a' / (name + '.npy'))), np.load(str(tmp_path / 'b' / (name + '.npy')))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+        total += os.path.getsize(str(tmp_path / 'a' / (name + '.npy')))
+    assert total <= budget
+    rows = np.load(str(tmp_path / 'a' / 'rows.npy'))
+    assert rows.dtype == np.float32 and rows.shape == (10000,) and np.all(np.diff(rows) > 0) and rows[-1] < 50000
+    kept = np.load(str(tmp_path / 'a' / 'kept.npy'))
+    assert kept.dtype == np.float64 and kept.tolist() == [[3, -1], [7, 2]]
+    assert np.load(str(tmp_path / 'a' / 'half.npy')).dtype == np.float32
+
+
 def test_objects_refuse_a_foreign_current_device(monkeypatch):
     """One process per GPU: an object built for cuda:1 used while cuda:0 is current must be refused (its kernels would be
     launched on the wrong device); same device: no complaint."""

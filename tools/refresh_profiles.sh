@@ -14,7 +14,7 @@ OUT=gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 ERR=$OUT/${TAG}_bench.err
-LEAN="--no-cpu-baseline --no-northstar --no-train-key --no-f32-key --no-repeats"
+LEAN="--full --no-cpu-baseline --no-northstar --no-train-key --no-f32-key --no-repeats"
 md5_of() { python -c "import sys,json; print(json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])['plan_md5'])" $1; }
 for W in 416 608; do
   if [ $W = 416 ]; then SH=""; SUF=""; B=32; else SH="--size 608 --batch 64"; SUF="_608"; B=64; fi
@@ -32,10 +32,10 @@ done
 cp $OUT/${TAG}_pmc_summary.txt $OUT/${PT}_pmc_summary.txt
 cp $OUT/${TAG}_bench_profiled.json $OUT/${PT}_bench_profiled.json
 # bench lines (un-profiled): 608 bs 64 alone and with NMS, the training step, then the full headline line (the driver's command)
-python bench.py --steps 10 --warmup 3 --size 608 --batch 64 --no-cpu-baseline > $OUT/${PT}_bench_608.json 2>> $ERR
-python bench.py --steps 10 --warmup 3 --size 608 --batch 64 --post nms --no-cpu-baseline --no-roofline > $OUT/${PT}_bench_608_nms.json 2>> $ERR
-python bench.py --mode train --steps 20 --warmup 3 > $OUT/${PT}_train_bench.json 2>> $ERR
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_train -o p -- python bench.py --mode train --steps 10 --warmup 2 > $OUT/${PT}_train_bench_profiled.json 2>> $ERR
+python bench.py --steps 10 --warmup 3 --size 608 --batch 64 --full --no-cpu-baseline > $OUT/${PT}_bench_608.json 2>> $ERR
+python bench.py --steps 10 --warmup 3 --size 608 --batch 64 --post nms --full --no-cpu-baseline --no-roofline > $OUT/${PT}_bench_608_nms.json 2>> $ERR
+python bench.py --mode train --steps 20 --warmup 3 --full > $OUT/${PT}_train_bench.json 2>> $ERR
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_train -o p -- python bench.py --mode train --steps 10 --warmup 2 --full > $OUT/${PT}_train_bench_profiled.json 2>> $ERR
 cp $OUT/${TAG}_prof_train/p_kernel_stats.csv $OUT/${PT}_train_kernel_stats.csv 2>/dev/null
 rm -rf $OUT/${TAG}_prof_train
 # (round 6) the training step's counters: HBM traffic per kernel (two passes) and MFMA-busy, 1 warm-up + 3 steps each; bench.py's
@@ -50,12 +50,12 @@ rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_
 python tools/pmc_mfma.py $OUT/${TAG}_pmc_tm $OUT/${PT}_train_pmc_mfma.json >> $OUT/${TAG}_pmc_summary.txt 2>&1
 rm -rf $OUT/${TAG}_pmc_tf $OUT/${TAG}_pmc_tw $OUT/${TAG}_pmc_tm
 cp $OUT/${TAG}_pmc_summary.txt $OUT/${PT}_pmc_summary.txt
-python bench.py --mode train --steps 20 --warmup 3 > $OUT/${PT}_train_bench.json 2>> $ERR        # (again: now with roofline.traffic)
+python bench.py --mode train --steps 20 --warmup 3 --full > $OUT/${PT}_train_bench.json 2>> $ERR        # (again: now with roofline.traffic)
 # (round 6) the split bf16 parity path (dtype bf16x3) on the headline workload: kernel trace + bench line
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_x3 -o p -- python bench.py --dtype bf16x3 --steps 20 --warmup 3 $LEAN > $OUT/${PT}_bench_x3_profiled.json 2>> $ERR
 cp $OUT/${TAG}_prof_x3/p_kernel_stats.csv $OUT/${PT}_x3_kernel_stats.csv 2>/dev/null
 rm -rf $OUT/${TAG}_prof_x3
-python bench.py --dtype bf16x3 --steps 20 --warmup 3 --no-cpu-baseline > $OUT/${PT}_bench_x3.json 2>> $ERR
-python bench.py --steps 20 --warmup 5 > $OUT/${PT}_bench.json 2>> $ERR
+python bench.py --dtype bf16x3 --steps 20 --warmup 3 --full --no-cpu-baseline > $OUT/${PT}_bench_x3.json 2>> $ERR
+python bench.py --steps 20 --warmup 5 --full > $OUT/${PT}_bench.json 2>> $ERR
 ls -la $OUT | grep ${PT}_
 tail -c 1500 $OUT/${PT}_bench.json
