@@ -23,7 +23,7 @@ extern "C" {
 #define YOLO_BF16 1
 #define YOLO_F16 2     /* IEEE half: the reference's own reduced precision (use_fp16 -> net.cast('float16'), car/YOLO.py:98-100; executor fp16 flag
                           yolo_gluon.py:204-214).  Inference entry points only (pack, fold, nchw<->nhwc, conv_fwd, stem, res_block); the
-                          training entries take YOLO_F32 | YOLO_BF16 */
+                          training entries take YOLO_F32 | YOLO_BF16 (and YOLO_BF16X3, below) */
 
 /* SPLIT bf16 ("bf16x3", round 6): the path on which the north-star tolerance (decoded boxes within 1e-3 of the fp32 reference) and the
  * bf16 MFMA rate meet.  A value v is stored as TWO bf16 numbers, hi = bf16(v) and lo = bf16(v - hi) (16 significant bits), and every
@@ -32,9 +32,14 @@ extern "C" {
  * per pixel a hi PLANE of Cp = round_up(C, 32) values (C real, the rest zero: whole 32-channel K-chunks), then -- `lo offset`
  * elements further (dense: Cp) -- the lo plane: dense pixel stride 2 * Cp elements of 2 bytes.  The kernels never write the pad
  * channels and read them as operands of zero weights: THE CALLER ZEROES A BUFFER WITH C % 32 != 0 ONCE (a NaN there would poison the
- * sums).  Inference entry points only: yolo_packed_weight_bytes / yolo_pack_conv_weights (image [w_hi | w_hi | w_lo] over
+ * sums).  Entry points that take it: yolo_packed_weight_bytes / yolo_pack_conv_weights (image [w_hi | w_hi | w_lo] over
  * 3 * Cp / 32 K-chunks; Cin % 8 == 0), yolo_conv_fwd (pipelined kernels; Cout % 8 == 0 unless out_f32; no stats / tail),
- * yolo_stem_conv_fwd.  Everything else returns YOLO_EUNSUPPORTED / YOLO_EINVAL for it. */
+ * yolo_stem_conv_fwd, and -- the split training step (revision 5) -- yolo_pack_conv_weights_dgrad (dgrad image as three K passes
+ * [w'_hi | w'_hi | w'_lo]), yolo_bn_train_fwd / _bwd / _fwd_pp / _bwd_pp, yolo_nchw_to_nhwc, yolo_upsample2x_concat (+ _bwd),
+ * yolo_dilate2x, yolo_gather_rows, yolo_bias_grad, yolo_add_split and yolo_conv_wgrad_split.  Their split tensors are dense
+ * (C logical channels, planes of round_up(C, 32)); values are read as hi + lo in fp32 and stored as hi = bf16_rne(v),
+ * lo = bf16_rne(v - hi).  Everything else returns YOLO_EUNSUPPORTED / YOLO_EINVAL for it (the _partials entries,
+ * yolo_conv_dgrad_s2, yolo_pack_batch_blocks, yolo_conv_wgrad / _algo and yolo_add among them). */
 #define YOLO_BF16X3 3
 /* The same scheme on IEEE-half pairs (22 significant bits; the dropped term is 2^-22 of a product): decoded boxes indistinguishable from
  * the fp32 path's (6e-5 on the D53 random-BN nets, where YOLO_BF16X3 measures 3e-4) at the same three MFMAs per product -- for data inside
@@ -48,9 +53,9 @@ extern "C" {
 
 /* ABI revision = the layout of every struct and the argument list of every entry below.  A caller compiled against another
  * revision must not call anything else: the library reads the WHOLE yolo_conv_desc on every call (revision 2 appended the
- * tail_* fields, revision 3 added YOLO_F16, revision 4 YOLO_BF16X3 and the *_lo_offset fields), so a shorter struct from an older header would be read past its end.
+ * tail_* fields, revision 3 added YOLO_F16, revision 4 YOLO_BF16X3 and the *_lo_offset fields, revision 5 the split training entries), so a shorter struct from an older header would be read past its end.
  * yolo_amd/lib.py:load() refuses a library whose yolo_version() differs from the YOLO_ABI_VERSION it was written against. */
-#define YOLO_ABI_VERSION 4
+#define YOLO_ABI_VERSION 5
 int yolo_version(void);
 
 /* ---- parameter preparation ------------------------------------------------------------- */
@@ -392,10 +397,24 @@ int yolo_conv_wgrad(const void* dy, const void* x, float* dw_oihw, int N, int H,
 int yolo_conv_wgrad_algo(const void* dy, const void* x, float* dw_oihw, int N, int H, int W, int Cin, int Cout,
                          int ksize, int stride, long long dy_pixel_stride, int dtype, void* workspace, int algo,
                          void* stream);
-/* db[c] += sum over npix rows of dy (row stride pixel_stride, 0 = C): YOLOOutput's bias gradient. */
+/* Split weight gradient (YOLO_BF16X3; yolo_conv_wgrad refuses split types): the same sum with dy and x as (hi, lo) pairs and
+ * every product taken as dy_hi x_hi + dy_hi x_lo + dy_lo x_hi on v_mfma_f32_32x32x16_bf16 (fp32 accumulation).  x: dense split
+ * (N,H,W,Cin), Cin % 8 == 0; dy rows: hi values at dy + p * dy_pixel_stride, lo values dy_lo_offset elements further (0, 0 =
+ * dense: lo offset round_up(Cout, 32), pixel stride twice that) -- the padded gradient rows of an output convolution are a
+ * slice of wider rows.  k in {1, 3}, stride in {1, 2}.  workspace: yolo_conv_wgrad_split_workspace_bytes(), ZERO-FILLED by the
+ * caller before its first use; every call leaves it zeroed again.  algo: 0 = the library's choice, 1 = 64 x 64 tiles,
+ * 2 = 128 x 128 tiles.  The kernel's offsets into x are 32-bit: a batch whose x reaches 4 GiB (both planes count) runs as several
+ * launches over slices of whole images; YOLO_EUNSUPPORTED only when ONE image's x does. */
+long long yolo_conv_wgrad_split_workspace_bytes(int Cin, int Cout, int ksize, int dtype);
+int yolo_conv_wgrad_split(const void* dy, const void* x, float* dw_oihw, int N, int H, int W, int Cin, int Cout,
+                          int ksize, int stride, long long dy_pixel_stride, long long dy_lo_offset, int dtype,
+                          void* workspace, int algo, void* stream);
+/* db[c] += sum over npix rows of dy (row stride pixel_stride, 0 = C; YOLO_BF16X3: 0 = 2 * round_up(C, 32), the lo value
+ * round_up(C, 32) behind the hi value): YOLOOutput's bias gradient. */
 int yolo_bias_grad(const void* dy, float* db, long long npix, int C, long long pixel_stride, int dtype,
                    void* stream);
-/* float32 (B, rows, [src strides]) C values per row -> dense (B*rows, Cpad) of `dtype`, zero padded. */
+/* float32 (B, rows, [src strides]) C values per row -> dense (B*rows, Cpad) of `dtype`, zero padded (YOLO_BF16X3: dense split
+ * rows of Cpad channels; the plane pad beyond Cpad is not written). */
 int yolo_gather_rows(const float* src, void* dst, int B, long long rows_per_batch, int C, int Cpad,
                      long long src_batch_stride, long long src_row_stride, int dtype, void* stream);
 /* D (N,H,W,C): D[n,2y,2x,:] = dy[n,y,x,:] (dy is (N,Ho,Wo,C)), zeros elsewhere: turns the stride-2 data
@@ -407,6 +426,9 @@ int yolo_dilate2x(const void* dy, void* d, int N, int H, int W, int Ho, int Wo, 
 int yolo_upsample2x_concat_bwd(const void* dcat, void* dup, void* droute, int N, int H, int W, int C1,
                                int C2, int accumulate_up, int accumulate_route, int dtype, void* stream);
 int yolo_add(const void* a, const void* b, void* y, long long n, int dtype, void* stream);
+/* The same for dense split tensors (YOLO_BF16X3) of npix pixels x C channels: an element count alone cannot locate a value's lo
+ * plane, which lies round_up(C, 32) behind its hi value.  Sums in fp32, stored as a pair; the pad channels are not written. */
+int yolo_add_split(const void* a, const void* b, void* y, long long npix, int C, int dtype, void* stream);
 
 /* _find_best + the scatter of _loss_mask (car/YOLO.py:401-480): labels (B,nobj,6+ncls)
  * [cls,y,x,h,w,rot,dist...] (cls < 0 = no object), anchors_ltrb (nbox,4) = _get_default_ltrb

@@ -869,7 +869,9 @@ static int pack_impl(const float* w_oihw, void* packed, int Cout, int Cin, int k
     const long long bytes = yolo_packed_weight_bytes(Cout, Cin, ksize, dtype);
     if (bytes < 0) return (int)bytes;
     const int Cout_pad = round_up(Cout, YOLO_COUT_PAD);
-    if (dtype_split(dtype) && dgrad) return YOLO_EUNSUPPORTED;
+    // split data-gradient images: the flipped / transposed image (dgrad 1) as three K passes [w'_hi | w'_hi | w'_lo], YOLO_BF16X3 only;
+    // the sub-pixel image (dgrad 2) has no split form
+    if (dtype_split(dtype) && (dgrad == 2 || (dgrad && dtype != YOLO_BF16X3))) return YOLO_EUNSUPPORTED;
     const int nchunks = (Cin * elem_size(dtype) + 63) / 64 * dtype_kpasses(dtype);
     const long long total = bytes / elem_size(dtype);
     const int grid = (int)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);

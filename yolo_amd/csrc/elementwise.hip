@@ -64,13 +64,34 @@ __global__ void nchw_to_nhwc_kernel(const float* __restrict__ x, T* __restrict__
     }
 }
 
+// split form (YOLO_BF16X3): the Cpad = 8 channels of a pixel as a hi and a lo octet, round_up(8, 32) = 32 elements apart (dense
+// split storage, pixel stride 64); the 24 pad channels of each plane are not written
+__global__ void nchw_to_nhwc_split_kernel(const float* __restrict__ x, uint16_t* __restrict__ y, int C, long long HW, long long total) {
+    const long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (p >= total) return;
+    const long long n = p / HW, hw = p - n * HW;
+    uint32_t h[4], l[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float a = (2 * q < C) ? x[(n * C + 2 * q) * HW + hw] : 0.f;
+        const float b = (2 * q + 1 < C) ? x[(n * C + 2 * q + 1) * HW + hw] : 0.f;
+        h[q] = pack_bf16x2(a, b);
+        l[q] = pack_bf16x2(a - bf16_bits_to_f32(h[q] & 0xffffu), b - bf16_bits_to_f32(h[q] >> 16));
+    }
+    uint4* dst = (uint4*)(y + p * 64);
+    dst[0] = make_uint4(h[0], h[1], h[2], h[3]);
+    dst[4] = make_uint4(l[0], l[1], l[2], l[3]);
+}
+
 extern "C" int yolo_nchw_to_nhwc(const float* x, void* y, int N, int C, int H, int W, int Cpad, int dtype,
                                  void* stream) {
     if (!x || !y || N <= 0 || C <= 0 || H <= 0 || W <= 0) return YOLO_EINVAL;
     if (Cpad != 8 || C > 8) return YOLO_EUNSUPPORTED;
     const long long HW = (long long)H * W, total = HW * N;
     const unsigned grid = (unsigned)((total + 255) / 256);
-    if (dtype == YOLO_BF16)
+    if (dtype == YOLO_BF16X3)
+        YOLO_LAUNCH(nchw_to_nhwc_split_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (uint16_t*)y, C, HW, total);
+    else if (dtype == YOLO_BF16)
         YOLO_LAUNCH((nchw_to_nhwc_kernel<bf16_t, 8>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x,
                            (bf16_t*)y, C, HW, total);
     else if (dtype == YOLO_F16)
@@ -160,9 +181,45 @@ __global__ void upsample_concat_kernel(const uint4* __restrict__ up, const uint4
     }
 }
 
+// split form: dense split up (C1), route (C2) and y (C1 + C2 channels); per output pixel and plane, 8-channel units of up then route
+// (C1 % 8 == 0 and C2 % 8 == 0); the pad channels of y are not written
+__global__ void upsample_concat_split_kernel(const uint16_t* __restrict__ up, const uint16_t* __restrict__ route,
+                                             uint16_t* __restrict__ y, int H, int W, int C1, int C2, long long total) {
+    const long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int U1 = C1 / 8, U = (C1 + C2) / 8;
+    const long long pix = idx / U;
+    const int q = (int)(idx - pix * U);
+    const long long ps1 = 2LL * round_up(C1, 32), ps2 = 2LL * round_up(C2, 32), psy = 2LL * round_up(C1 + C2, 32);
+    const uint16_t* s;
+    long long lo;
+    if (q >= U1) {
+        s = route + pix * ps2 + (q - U1) * 8;
+        lo = ps2 / 2;
+    } else {
+        const long long HW = (long long)H * W;
+        const long long n = pix / HW;
+        const int hw = (int)(pix - n * HW);
+        const int yy = hw / W, xx = hw - yy * W;
+        s = up + ((n * (H / 2) + (yy >> 1)) * (W / 2) + (xx >> 1)) * ps1 + q * 8;
+        lo = ps1 / 2;
+    }
+    uint16_t* o = y + pix * psy + q * 8;
+    *(uint4*)o = *(const uint4*)s;
+    *(uint4*)(o + psy / 2) = *(const uint4*)(s + lo);
+}
+
 extern "C" int yolo_upsample2x_concat(const void* up, const void* route, void* y, int N, int H, int W, int C1,
                                       int C2, int dtype, void* stream) {
     if (!up || !route || !y || N <= 0 || H <= 0 || W <= 0 || C1 <= 0 || C2 <= 0) return YOLO_EINVAL;
+    if (dtype == YOLO_BF16X3 && !(H & 1) && !(W & 1)) {
+        if ((C1 % 8) || (C2 % 8)) return YOLO_EUNSUPPORTED;
+        const long long total = (long long)N * H * W * ((C1 + C2) / 8);
+        YOLO_LAUNCH(upsample_concat_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                    (const uint16_t*)up, (const uint16_t*)route, (uint16_t*)y, H, W, C1, C2, total);
+        YOLO_LAUNCH_CHECK();
+        return YOLO_OK;
+    }
     if ((H & 1) || (W & 1) || !dtype_plain(dtype)) return YOLO_EINVAL;
     const int es = elem_size(dtype);
     if ((C1 * es) % 16 || (C2 * es) % 16) return YOLO_EUNSUPPORTED;

@@ -36,6 +36,44 @@ template <typename T> __device__ __forceinline__ void store1(T* p, float v);
 template <> __device__ __forceinline__ void store1<float>(float* p, float v) { *p = v; }
 template <> __device__ __forceinline__ void store1<bf16_t>(bf16_t* p, float v) { p->bits = (uint16_t)f32_to_bf16_bits(v); }
 
+// The same accesses on a split tensor (YOLO_BF16X3): a value is READ as hi + lo in fp32 and STORED as hi = bf16_rne(v),
+// lo = bf16_rne(v - hi); its lo plane sits `lo` elements behind the hi plane.  For the single-plane types `lo` is not used.
+// dense_ps / dense_lo: pixel stride and lo offset of a dense (N,H,W,C) tensor (split: per pixel round_up(C, 32) hi values, then
+// as many lo values; the pad channels are never read or written here).
+template <typename T> __host__ __device__ __forceinline__ long long dense_ps(int C) { return IsSplit<T>::value ? 2LL * round_up(C, 32) : C; }
+template <typename T> __host__ __device__ __forceinline__ int dense_lo(int C) { return IsSplit<T>::value ? round_up(C, 32) : 0; }
+// bytes an HBM pass moves per value (the BatchNorm partition)
+template <typename T> constexpr int value_bytes() { return IsSplit<T>::value ? 4 : (int)sizeof(T); }
+__device__ __forceinline__ uint32_t split_lo_bf16x2(float a, float b, uint32_t hi) {
+    return pack_bf16x2(a - bf16_bits_to_f32(hi & 0xffffu), b - bf16_bits_to_f32(hi >> 16));
+}
+template <typename T> __device__ __forceinline__ void load8s(const T* p, int, float (&v)[8]) { load8<T>(p, v); }
+template <> __device__ __forceinline__ void load8s<bf16x3_t>(const bf16x3_t* p, int lo, float (&v)[8]) {
+    float h[8], l[8];
+    load8<bf16_t>((const bf16_t*)p, h);
+    load8<bf16_t>((const bf16_t*)p + lo, l);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = h[e] + l[e];
+}
+template <typename T> __device__ __forceinline__ void store8s(T* p, int, const float (&v)[8]) { store8<T>(p, v); }
+template <> __device__ __forceinline__ void store8s<bf16x3_t>(bf16x3_t* p, int lo, const float (&v)[8]) {
+    uint32_t h[4], l[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { h[q] = pack_bf16x2(v[2 * q], v[2 * q + 1]); l[q] = split_lo_bf16x2(v[2 * q], v[2 * q + 1], h[q]); }
+    *(uint4*)p = make_uint4(h[0], h[1], h[2], h[3]);
+    *(uint4*)((bf16_t*)p + lo) = make_uint4(l[0], l[1], l[2], l[3]);
+}
+template <typename T> __device__ __forceinline__ float load1s(const T* p, int) { return load1<T>(p); }
+template <> __device__ __forceinline__ float load1s<bf16x3_t>(const bf16x3_t* p, int lo) {
+    return bf16_bits_to_f32(p->bits) + bf16_bits_to_f32(p[lo].bits);
+}
+template <typename T> __device__ __forceinline__ void store1s(T* p, int, float v) { store1<T>(p, v); }
+template <> __device__ __forceinline__ void store1s<bf16x3_t>(bf16x3_t* p, int lo, float v) {
+    const uint32_t h = f32_to_bf16_bits(v);
+    p->bits = (uint16_t)h;
+    p[lo].bits = (uint16_t)f32_to_bf16_bits(v - bf16_bits_to_f32(h));
+}
+
 // ------------------------------------------------------------------------------------------------
 // BatchNorm (train): per-channel batch statistics over (N,H,W) of an NHWC tensor (C % 8 == 0).
 // Both passes are HBM-bound.  Thread = one 8-channel octet x one pixel lane of a block-owned pixel range:
@@ -74,6 +112,10 @@ static void bn_partition(long long npix, int C, int elem, bool reduces, int* ppb
 template <typename T> __device__ __forceinline__ float ld1(const T* p);
 template <> __device__ __forceinline__ float ld1<float>(const float* p) { return *p; }
 template <> __device__ __forceinline__ float ld1<bf16_t>(const bf16_t* p) { return bf16_bits_to_f32(*reinterpret_cast<const uint16_t*>(p)); }
+template <typename T> __device__ __forceinline__ float ld1s(const T* p, int) { return ld1<T>(p); }
+template <> __device__ __forceinline__ float ld1s<bf16x3_t>(const bf16x3_t* p, int lo) {
+    return bf16_bits_to_f32(*reinterpret_cast<const uint16_t*>(p)) + bf16_bits_to_f32(*reinterpret_cast<const uint16_t*>(p + lo));
+}
 
 // MODE 0: sums[0..C) = sum(y), sums[C..2C) = sum(y*y) -- or, with `shift`, the same sums of (y - k_c), k_c = the channel's value
 //         at pixel 0: a one-pass variance from fp32 partial sums loses digits when mean^2 >> variance (0.4 % in invstd at a ratio of
@@ -96,6 +138,8 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const T* __restrict__ y,
     constexpr int U = MODE == 0 ? 8 : YOLO_BNR_U1;
     __shared__ float red[2][256][8];
     const int noct = C >> 3;
+    const long long PS = dense_ps<T>(C);                        // pixel stride (C; split: both padded planes)
+    const int LO = dense_lo<T>(C);
     const int goct = BN_CG / 8;                                 // octets of a channel group
     const int per = noct < goct ? noct : goct;                  // octets handled by this block
     const int lanes = 256 / per;                                // pixel lanes per octet in this block
@@ -112,7 +156,7 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const T* __restrict__ y,
             float mu[8], is[8], g[8], b[8];
             if (MODE == 0) {
 #pragma unroll
-                for (int e = 0; e < 8; ++e) mu[e] = shift ? ld1<T>(y + oct * 8 + e) : 0.f;      // the pivots k_c
+                for (int e = 0; e < 8; ++e) mu[e] = shift ? ld1s<T>(y + oct * 8 + e, LO) : 0.f;      // the pivots k_c
             }
             if (MODE == 1) {
 #pragma unroll
@@ -136,16 +180,16 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const T* __restrict__ y,
                 float v[U][8], d[U][8];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    load8<T>(yp + (p + (long long)u * lanes) * C, v[u]);
-                    if (MODE == 1) load8<T>(dp + (p + (long long)u * lanes) * C, d[u]);
+                    load8s<T>(yp + (p + (long long)u * lanes) * PS, LO, v[u]);
+                    if (MODE == 1) load8s<T>(dp + (p + (long long)u * lanes) * PS, LO, d[u]);
                 }
 #pragma unroll
                 for (int u = 0; u < U; ++u) accum(v[u], MODE == 1 ? d[u] : v[u]);
             }
             for (; p < p1; p += lanes) {
                 float v[8], d[8];
-                load8<T>(yp + p * C, v);
-                if (MODE == 1) load8<T>(dp + p * C, d);
+                load8s<T>(yp + p * PS, LO, v);
+                if (MODE == 1) load8s<T>(dp + p * PS, LO, d);
                 accum(v, MODE == 1 ? d : v);
             }
         }
@@ -171,13 +215,13 @@ template <typename T>
 __global__ void bn_finalize_kernel(double* __restrict__ sums, float* __restrict__ mean,
                                    float* __restrict__ invstd, float* __restrict__ running_mean,
                                    float* __restrict__ running_var, int C, double inv_n, float eps, float momentum,
-                                   const T* __restrict__ pivot) {        // pivot: pixel 0 of y when the sums are shifted, else NULL
+                                   const T* __restrict__ pivot, int pivot_lo) {   // pivot: pixel 0 of y when the sums are shifted, else NULL
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     const double d = sums[c] * inv_n;
     double v = sums[C + c] * inv_n - d * d;
     if (v < 0) v = 0;
-    const double m = d + (pivot ? (double)ld1<T>(pivot + c) : 0.0);
+    const double m = d + (pivot ? (double)ld1s<T>(pivot + c, pivot_lo) : 0.0);
     mean[c] = (float)m;
     invstd[c] = (float)(1.0 / sqrt(v + (double)eps));
     sums[c] = 0.0;                                   // leave the workspace zeroed for the next call
@@ -232,6 +276,8 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ y, 
 #endif
     constexpr int U = MODE == 0 ? YOLO_BN_U0 : YOLO_BN_U1;
     const int noct = C >> 3;
+    const long long PS = dense_ps<T>(C);                        // pixel stride (C; split: both padded planes)
+    const int LO = dense_lo<T>(C);
     const int per = noct < 256 ? noct : 256;
     const int lanes = 256 / per;
     const long long p0 = (long long)blockIdx.x * pix_per_block;
@@ -242,7 +288,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ y, 
                 const double d = f.sums[c] * f.inv_n;
                 double v = f.sums[C + c] * f.inv_n - d * d;
                 if (v < 0) v = 0;
-                const double m = d + (f.shifted ? (double)ld1<T>(y + c) : 0.0);
+                const double m = d + (f.shifted ? (double)ld1s<T>(y + c, LO) : 0.0);
                 f.mean_out[c] = (float)m;
                 f.invstd_out[c] = (float)(1.0 / sqrt(v + (double)f.eps));
                 if (f.running_mean) {
@@ -268,7 +314,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ y, 
                 const double d = f.sums[c] * f.inv_n;
                 double v = f.sums[C + c] * f.inv_n - d * d;
                 if (v < 0) v = 0;
-                const double m = d + (f.shifted ? (double)ld1<T>(y + c) : 0.0);
+                const double m = d + (f.shifted ? (double)ld1s<T>(y + c, LO) : 0.0);
                 mu[e] = (float)m; is[e] = (float)(1.0 / sqrt(v + (double)f.eps));
             } else {
                 mu[e] = mean[c]; is[e] = invstd[c];
@@ -316,21 +362,21 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ y, 
             float v[U][8], o[U][8], r[8];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                load8<T>(y + (p + (long long)u * lanes) * C + co, v[u]);
-                if (other) load8<T>(other + (p + (long long)u * lanes) * C + co, o[u]);
+                load8s<T>(y + (p + (long long)u * lanes) * PS + co, LO, v[u]);
+                if (other) load8s<T>(other + (p + (long long)u * lanes) * PS + co, LO, o[u]);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 apply(v[u], other ? o[u] : v[u], r);
-                store8<T>(out + (p + (long long)u * lanes) * C + co, r);
+                store8s<T>(out + (p + (long long)u * lanes) * PS + co, LO, r);
             }
         }
         for (; p < p1; p += lanes) {
             float v[8], o[8], r[8];
-            load8<T>(y + p * C + co, v);
-            if (other) load8<T>(other + p * C + co, o);
+            load8s<T>(y + p * PS + co, LO, v);
+            if (other) load8s<T>(other + p * PS + co, LO, o);
             apply(v, other ? o : v, r);
-            store8<T>(out + p * C + co, r);
+            store8s<T>(out + p * PS + co, LO, r);
         }
     }
 }
@@ -385,8 +431,8 @@ static int bn_fwd_t(const T* y, const float* gamma, const float* beta, const T* 
                     const float* part = nullptr, int part_rows = 0, int part_cp = 0) {
     (void)hipGetLastError();
     int ppb, ppa; unsigned nb, na;
-    bn_partition(npix, C, (int)sizeof(T), true, &ppb, &nb);
-    bn_partition(npix, C, (int)sizeof(T), false, &ppa, &na);
+    bn_partition(npix, C, value_bytes<T>(), true, &ppb, &nb);
+    bn_partition(npix, C, value_bytes<T>(), false, &ppa, &na);
     if (part)       // the producing convolution already took the sums (its statistics epilogue): no pass over y
         bn_stats_finish(part, part_rows, C, part_cp, workspace, st);
     else                                                      // (shifted sums: see bn_reduce_kernel)
@@ -403,7 +449,7 @@ static int bn_fwd_t(const T* y, const float* gamma, const float* beta, const T* 
         return YOLO_OK;
     }
     YOLO_LAUNCH(bn_finalize_kernel<T>, dim3((C + 255) / 256), dim3(256), 0, st, workspace, mean, invstd, running_mean,
-                running_var, C, 1.0 / (double)npix, eps, momentum, part ? (const T*)nullptr : y);
+                running_var, C, 1.0 / (double)npix, eps, momentum, part ? (const T*)nullptr : y, dense_lo<T>(C));
     YOLO_LAUNCH((bn_apply_kernel<T, 0>), dim3(na), dim3(256), 0, st, y, residual, mean, invstd, gamma, beta,
                 (const float*)nullptr, (const float*)nullptr, 0.f, z, C, npix, ppa, slope, f);
     YOLO_LAUNCH_CHECK();
@@ -419,6 +465,9 @@ extern "C" int yolo_bn_train_fwd(const void* y, const float* gamma, const float*
     if (dtype == YOLO_BF16)
         return bn_fwd_t<bf16_t>((const bf16_t*)y, gamma, beta, (const bf16_t*)residual, (bf16_t*)z, mean, invstd,
                                 running_mean, running_var, workspace, npix, C, eps, momentum, slope, (hipStream_t)stream);
+    if (dtype == YOLO_BF16X3)
+        return bn_fwd_t<bf16x3_t>((const bf16x3_t*)y, gamma, beta, (const bf16x3_t*)residual, (bf16x3_t*)z, mean, invstd,
+                                  running_mean, running_var, workspace, npix, C, eps, momentum, slope, (hipStream_t)stream);
     if (dtype == YOLO_F32)
         return bn_fwd_t<float>((const float*)y, gamma, beta, (const float*)residual, (float*)z, mean, invstd,
                                running_mean, running_var, workspace, npix, C, eps, momentum, slope, (hipStream_t)stream);
@@ -432,8 +481,8 @@ static int bn_bwd_t(const T* dz, const T* y, const float* mean, const float* inv
                     const float* part = nullptr, int part_rows = 0, int part_cp = 0) {
     (void)hipGetLastError();
     int ppb, ppa; unsigned nb, na;
-    bn_partition(npix, C, (int)sizeof(T), true, &ppb, &nb);
-    bn_partition(npix, C, (int)sizeof(T), false, &ppa, &na);
+    bn_partition(npix, C, value_bytes<T>(), true, &ppb, &nb);
+    bn_partition(npix, C, value_bytes<T>(), false, &ppa, &na);
     if (part)       // the data gradient that produced dz already took sum(da), sum(da * xhat): no pass over dz and y
         bn_stats_finish(part, part_rows, C, part_cp, workspace, st);
     else
@@ -463,6 +512,9 @@ extern "C" int yolo_bn_train_bwd(const void* dz, const void* y, const float* mea
     if (dtype == YOLO_BF16)
         return bn_bwd_t<bf16_t>((const bf16_t*)dz, (const bf16_t*)y, mean, invstd, gamma, beta, (bf16_t*)dy, dgamma, dbeta,
                                 workspace, npix, C, slope, (hipStream_t)stream);
+    if (dtype == YOLO_BF16X3)
+        return bn_bwd_t<bf16x3_t>((const bf16x3_t*)dz, (const bf16x3_t*)y, mean, invstd, gamma, beta, (bf16x3_t*)dy, dgamma,
+                                  dbeta, workspace, npix, C, slope, (hipStream_t)stream);
     if (dtype == YOLO_F32)
         return bn_bwd_t<float>((const float*)dz, (const float*)y, mean, invstd, gamma, beta, (float*)dy, dgamma, dbeta,
                                workspace, npix, C, slope, (hipStream_t)stream);
@@ -486,6 +538,10 @@ extern "C" int yolo_bn_train_fwd_pp(const void* y, const float* gamma, const flo
     if (dtype == YOLO_BF16)
         return bn_fwd_t<bf16_t>((const bf16_t*)y, gamma, beta, (const bf16_t*)residual, (bf16_t*)z, mean, invstd,
                                 running_mean, running_var, workspace, npix, C, eps, momentum, slope, (hipStream_t)stream, true, zero_next, zero_next_count);
+    if (dtype == YOLO_BF16X3)
+        return bn_fwd_t<bf16x3_t>((const bf16x3_t*)y, gamma, beta, (const bf16x3_t*)residual, (bf16x3_t*)z, mean, invstd,
+                                  running_mean, running_var, workspace, npix, C, eps, momentum, slope, (hipStream_t)stream, true, zero_next,
+                                  zero_next_count);
     if (dtype == YOLO_F32)
         return bn_fwd_t<float>((const float*)y, gamma, beta, (const float*)residual, (float*)z, mean, invstd,
                                running_mean, running_var, workspace, npix, C, eps, momentum, slope, (hipStream_t)stream, true, zero_next, zero_next_count);
@@ -502,6 +558,9 @@ extern "C" int yolo_bn_train_bwd_pp(const void* dz, const void* y, const float* 
     if (dtype == YOLO_BF16)
         return bn_bwd_t<bf16_t>((const bf16_t*)dz, (const bf16_t*)y, mean, invstd, gamma, beta, (bf16_t*)dy, dgamma, dbeta,
                                 workspace, npix, C, slope, (hipStream_t)stream, true, zero_next, zero_next_count);
+    if (dtype == YOLO_BF16X3)
+        return bn_bwd_t<bf16x3_t>((const bf16x3_t*)dz, (const bf16x3_t*)y, mean, invstd, gamma, beta, (bf16x3_t*)dy, dgamma,
+                                  dbeta, workspace, npix, C, slope, (hipStream_t)stream, true, zero_next, zero_next_count);
     if (dtype == YOLO_F32)
         return bn_bwd_t<float>((const float*)dz, (const float*)y, mean, invstd, gamma, beta, (float*)dy, dgamma, dbeta,
                                workspace, npix, C, slope, (hipStream_t)stream, true, zero_next, zero_next_count);
@@ -774,6 +833,168 @@ static void wgrad_bf16_launch(const uint16_t* dy, const uint16_t* x, float* ws, 
     slices = (chunks + cps - 1) / cps;
     YOLO_LAUNCH((wgrad_bf16_kernel<MI, NI>), dim3((unsigned)(tiles_ci * tiles_co), taps, (unsigned)slices), dim3(256), 0, st,
                 dy, x, ws, N, H, W, Cin, Ho, Wo, Cout, ksize, stride, ps, tiles_ci, cps, slices > 1 ? 1 : 0,
+                make_fastdiv((unsigned)Ho * Wo), make_fastdiv((unsigned)Wo));
+}
+
+// ------------------------------------------------------------------------------------------------
+// SPLIT weight gradient (YOLO_BF16X3): the per-tap kernel above on (hi, lo) pairs.  dy and x each come as two bf16 planes;
+// a K-chunk of SWG_KC pixels stages BOTH planes of both operands in LDS, and every fragment pair issues three MFMAs,
+// dy_hi x_hi + dy_hi x_lo + dy_lo x_hi (the dy_lo x_lo term, 2^-16 of a product, is dropped -- the split convolution's
+// own rule), accumulated in fp32.  Block = (MI*64) cout x (NI*64) cin x one tap, 4 waves; result [tap][Cout][Cin] fp32
+// (atomics when the pixel range is split), folded into OIHW by wgrad_finish_kernel.  32 pixels per chunk: four planes
+// of 64 pixels would take 72 KB of LDS at 128 x 128 and halve the resident blocks.
+// ------------------------------------------------------------------------------------------------
+constexpr int SWG_KC = 32;
+
+template <int MI, int NI>
+__global__ __launch_bounds__(256) void wgrad_split_kernel(const uint16_t* __restrict__ dy, const uint16_t* __restrict__ x,
+                                                          float* __restrict__ dwt, int N, int H, int W, int Cin, int Ho,
+                                                          int Wo, int Cout, int ks, int stride, long long dy_ps, int dy_lo,
+                                                          long long x_ps, int x_lo, int tiles_ci, int chunks_per_slice,
+                                                          int use_atomic, FastDiv d_howo, FastDiv d_wo) {
+    constexpr int BM = MI * 64, BN = NI * 64;
+    constexpr int PA = BM * 2 + 32, PB = BN * 2 + 32;            // LDS pitches (padded: conflict-free transposing reads)
+    constexpr int UA = SWG_KC * (BM / 8) / 256, UB = SWG_KC * (BN / 8) / 256;   // 16-byte units per thread, plane and chunk
+    static_assert(UA >= 1 && UB >= 1, "tile too small for the chunk");
+    __shared__ __attribute__((aligned(16))) char smem[2 * SWG_KC * (PA + PB)];
+    char* dyh = smem;
+    char* dyl = smem + SWG_KC * PA;
+    char* xh = smem + 2 * SWG_KC * PA;
+    char* xl = xh + SWG_KC * PB;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave & 1, wn = wave >> 1;
+    const int tile = blockIdx.x;
+    const int tci = tile % tiles_ci, tco = tile / tiles_ci;
+    const int co0 = tco * BM, ci0 = tci * BN;
+    const int tap = blockIdx.y, kh = tap / ks, kw = tap - kh * ks, pad = ks / 2;
+    const long long P = (long long)N * Ho * Wo;
+    const long long c_first = (long long)blockIdx.z * chunks_per_slice;
+    const long long c_last = min(c_first + chunks_per_slice, (P + SWG_KC - 1) / SWG_KC);
+    uint4 drh[UA], drl[UA], xrh[UB], xrl[UB];
+    // range-checked buffer loads as in wgrad_bf16_kernel: a unit that must read zeros gets an out-of-range offset (-1)
+    typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
+    int d_off[UA];
+#pragma unroll
+    for (int j = 0; j < UA; ++j) {
+        const int u = tid + j * 256;
+        const int px = u / (BM / 8), part = u % (BM / 8);
+        d_off[j] = (co0 + part * 8 < Cout) ? (int)((px * dy_ps + part * 8) * 2) : -1;
+    }
+    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (int)0xffffffffu, 0x00020000);
+    auto load_chunk = [&](long long c) {
+        const long long p0 = c * SWG_KC;
+        const int left = (int)min((long long)SWG_KC, P - p0);                // live pixels of this chunk
+        const __amdgpu_buffer_rsrc_t rs_d = __builtin_amdgcn_make_buffer_rsrc((void*)(dy + p0 * dy_ps + co0), 0, 0x7fffffff, 0x00020000);
+#pragma unroll
+        for (int j = 0; j < UA; ++j) {
+            const int u = tid + j * 256;
+            const bool ok = u / (BM / 8) < left && d_off[j] >= 0;
+            const u32x4_t a = __builtin_amdgcn_raw_buffer_load_b128(rs_d, ok ? d_off[j] : -1, 0, 0);
+            const u32x4_t b = __builtin_amdgcn_raw_buffer_load_b128(rs_d, ok ? d_off[j] + dy_lo * 2 : -1, 0, 0);
+            drh[j] = make_uint4(a.x, a.y, a.z, a.w);
+            drl[j] = make_uint4(b.x, b.y, b.z, b.w);
+        }
+#pragma unroll
+        for (int j = 0; j < UB; ++j) {
+            const int u = tid + j * 256;
+            const int px = u / (BN / 8), part = u % (BN / 8);
+            const int p = (int)p0 + px;
+            const int n = fdiv(p, d_howo);
+            const int rem = p - n * Ho * Wo;
+            const int oy = fdiv(rem, d_wo), ox = rem - oy * Wo;
+            const int iy = oy * stride + kh - pad, ix = ox * stride + kw - pad;
+            const bool ok = px < left && ci0 + part * 8 < Cin && iy >= 0 && iy < H && ix >= 0 && ix < W;
+            const unsigned off = ((unsigned)((n * H + iy) * W + ix) * (unsigned)x_ps + (unsigned)(ci0 + part * 8)) * 2u;
+            const u32x4_t a = __builtin_amdgcn_raw_buffer_load_b128(rs_x, ok ? (int)off : -1, 0, 0);
+            const u32x4_t b = __builtin_amdgcn_raw_buffer_load_b128(rs_x, ok ? (int)(off + (unsigned)x_lo * 2u) : -1, 0, 0);
+            xrh[j] = make_uint4(a.x, a.y, a.z, a.w);
+            xrl[j] = make_uint4(b.x, b.y, b.z, b.w);
+        }
+    };
+    f32x16 acc[MI][NI];
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+    if (c_first < c_last) load_chunk(c_first);
+    for (long long c = c_first; c < c_last; ++c) {
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < UA; ++j) {
+            const int u = tid + j * 256;
+            const int o = (u / (BM / 8)) * PA + (u % (BM / 8)) * 16;
+            *(uint4*)(dyh + o) = drh[j];
+            *(uint4*)(dyl + o) = drl[j];
+        }
+#pragma unroll
+        for (int j = 0; j < UB; ++j) {
+            const int u = tid + j * 256;
+            const int o = (u / (BN / 8)) * PB + (u % (BN / 8)) * 16;
+            *(uint4*)(xh + o) = xrh[j];
+            *(uint4*)(xl + o) = xrl[j];
+        }
+        __syncthreads();
+        if (c + 1 < c_last) load_chunk(c + 1);
+#pragma unroll
+        for (int kk = 0; kk < SWG_KC / 16; ++kk) {
+            uint4 ah[MI], al[MI], bh[NI], bl[NI];
+#pragma unroll
+            for (int mi = 0; mi < MI; ++mi) {
+                ah[mi] = tr_frag<PA>(dyh, kk * 16, (wm * MI + mi) * 32, lane);
+                al[mi] = tr_frag<PA>(dyl, kk * 16, (wm * MI + mi) * 32, lane);
+            }
+#pragma unroll
+            for (int ni = 0; ni < NI; ++ni) {
+                bh[ni] = tr_frag<PB>(xh, kk * 16, (wn * NI + ni) * 32, lane);
+                bl[ni] = tr_frag<PB>(xl, kk * 16, (wn * NI + ni) * 32, lane);
+            }
+#pragma unroll
+            for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < NI; ++ni) {
+                    acc[mi][ni] = mfma16<bf16_t>(ah[mi], bh[ni], acc[mi][ni]);
+                    acc[mi][ni] = mfma16<bf16_t>(ah[mi], bl[ni], acc[mi][ni]);
+                    acc[mi][ni] = mfma16<bf16_t>(al[mi], bh[ni], acc[mi][ni]);
+                }
+        }
+    }
+    const int l31 = lane & 31, h = lane >> 5;
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni) {
+            const int ci = ci0 + (wn * NI + ni) * 32 + l31;
+            if (ci >= Cin) continue;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int co = co0 + (wm * MI + mi) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                if (co >= Cout) continue;
+                float* dst = dwt + ((long long)tap * Cout + co) * Cin + ci;
+                if (use_atomic) atomicAdd(dst, acc[mi][ni][r]);
+                else *dst = acc[mi][ni][r];
+            }
+        }
+}
+
+template <int MI, int NI>
+static void wgrad_split_launch(const uint16_t* dy, const uint16_t* x, float* ws, int N, int H, int W, int Cin, int Ho, int Wo,
+                               int Cout, int ksize, int stride, long long dy_ps, int dy_lo, long long x_ps, int x_lo,
+                               bool force_atomic, hipStream_t st) {
+    constexpr int BM = MI * 64, BN = NI * 64;
+    const int tiles_ci = (Cin + BN - 1) / BN, tiles_co = (Cout + BM - 1) / BM, taps = ksize * ksize;
+    const long long chunks = ((long long)N * Ho * Wo + SWG_KC - 1) / SWG_KC;
+    const long long tiles = (long long)tiles_ci * tiles_co * taps;
+    const long long target = MI * NI == 1 ? 1536 : 768;         // about three resident rounds of blocks
+    long long slices = target / tiles;
+    if (slices > chunks / 32) slices = chunks / 32;              // at least 32 chunks (1024 pixels) per slice: each ends in atomics
+    if (slices < 1) slices = 1;
+    const int cps = (int)((chunks + slices - 1) / slices);
+    slices = (chunks + cps - 1) / cps;
+    YOLO_LAUNCH((wgrad_split_kernel<MI, NI>), dim3((unsigned)(tiles_ci * tiles_co), taps, (unsigned)slices), dim3(256), 0, st,
+                dy, x, ws, N, H, W, Cin, Ho, Wo, Cout, ksize, stride, dy_ps, dy_lo, x_ps, x_lo, tiles_ci, cps,
+                (slices > 1 || force_atomic) ? 1 : 0,
                 make_fastdiv((unsigned)Ho * Wo), make_fastdiv((unsigned)Wo));
 }
 
@@ -1312,6 +1533,58 @@ extern "C" int yolo_conv_wgrad_algo(const void* dy, const void* x, float* dw_oih
     return YOLO_OK;
 }
 
+// Split weight gradient (YOLO_BF16X3).  algo 0 = the library's choice, 1 = 64 x 64 tiles, 2 = 128 x 128 tiles.
+extern "C" long long yolo_conv_wgrad_split_workspace_bytes(int Cin, int Cout, int ksize, int dtype) {
+    if (Cin <= 0 || Cout <= 0 || (ksize != 1 && ksize != 3) || dtype != YOLO_BF16X3) return YOLO_EINVAL;
+    return (long long)Cin * Cout * ksize * ksize * 4;
+}
+
+extern "C" int yolo_conv_wgrad_split(const void* dy, const void* x, float* dw_oihw, int N, int H, int W, int Cin, int Cout,
+                                     int ksize, int stride, long long dy_pixel_stride, long long dy_lo_offset, int dtype,
+                                     void* workspace, int algo, void* stream) {
+    if (!dy || !x || !dw_oihw || !workspace || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return YOLO_EINVAL;
+    if (algo < 0 || algo > 2 || dy_pixel_stride < 0 || dy_lo_offset < 0) return YOLO_EINVAL;
+    if (dtype != YOLO_BF16X3) return YOLO_EINVAL;
+    if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2) || (Cin % 8)) return YOLO_EUNSUPPORTED;
+    const long long lo = dy_lo_offset ? dy_lo_offset : round_up(Cout, 32);
+    const long long ps = dy_pixel_stride ? dy_pixel_stride : 2 * lo;
+    // the lo plane of every dy row lies after its hi values and inside the pixel (rows of at least the 8-channel units read)
+    if (lo < round_up(Cout, 8) || ps < lo + round_up(Cout, 8) || (ps % 8) || (lo % 8)) return YOLO_EINVAL;
+    const int pad = ksize / 2;
+    const int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
+    const long long x_ps = dense_ps<bf16x3_t>(Cin);
+    const int x_lo = dense_lo<bf16x3_t>(Cin);
+    // The kernel's buffer offsets into x are 32-bit (dy offsets are relative to a chunk): a batch whose x reaches 4 GiB -- both planes
+    // count, so at half the images of the bf16 path -- runs as several launches over slices of whole images, each below the limit,
+    // all accumulating into the workspace with atomics.
+    const long long img_bytes = (long long)H * W * x_ps * 2;
+    long long per = N;
+    if (per * img_bytes >= 0xffffff00LL) per = (0xffffff00LL - 1) / img_bytes;
+    if (per * Ho * Wo >= 0x7fffffffLL) per = (0x7fffffffLL - 1) / ((long long)Ho * Wo);
+    if (per < 1 || lo * 2 >= 0x7fff0000LL) return YOLO_EUNSUPPORTED;            // (one image alone past the limit)
+    hipStream_t st = (hipStream_t)stream;
+    (void)hipGetLastError();
+    const int taps = ksize * ksize;
+    const long long total = (long long)Cin * Cout * taps;
+    const int variant = algo ? algo : ((Cin <= 64 || Cout <= 64) ? 1 : 2);
+    const bool sliced = per < N;
+    for (long long n0 = 0; n0 < N; n0 += per) {
+        const int n = (int)min(per, (long long)N - n0);
+        const uint16_t* d16 = (const uint16_t*)dy + n0 * Ho * Wo * ps;
+        const uint16_t* x16 = (const uint16_t*)x + n0 * H * W * x_ps;
+        if (variant == 1)
+            wgrad_split_launch<1, 1>(d16, x16, (float*)workspace, n, H, W, Cin, Ho, Wo, Cout, ksize, stride, ps, (int)lo, x_ps, x_lo,
+                                     sliced, st);
+        else
+            wgrad_split_launch<2, 2>(d16, x16, (float*)workspace, n, H, W, Cin, Ho, Wo, Cout, ksize, stride, ps, (int)lo, x_ps, x_lo,
+                                     sliced, st);
+    }
+    YOLO_LAUNCH(wgrad_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (float*)workspace, dw_oihw,
+                Cout, Cin, taps, total);
+    YOLO_LAUNCH_CHECK();
+    return YOLO_OK;
+}
+
 // column sums: db[c] += sum_p dy[p*ps + c]   (bias gradient of YOLOOutput's conv)
 template <typename T>
 __global__ __launch_bounds__(256) void bias_grad_kernel(const T* __restrict__ dy, float* __restrict__ db, int C,
@@ -1324,14 +1597,30 @@ __global__ __launch_bounds__(256) void bias_grad_kernel(const T* __restrict__ dy
         atomicAdd(&db[c], s);
     }
 }
+// split form: the lo plane `lo` elements behind the hi plane, each value read as hi + lo
+__global__ __launch_bounds__(256) void bias_grad_split_kernel(const bf16x3_t* __restrict__ dy, float* __restrict__ db, int C,
+                                                              long long npix, long long ps, int lo, int pix_per_block) {
+    const long long p0 = (long long)blockIdx.x * pix_per_block;
+    const long long p1 = min(p0 + pix_per_block, npix);
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        float s = 0.f;
+        for (long long p = p0; p < p1; ++p) s += load1s<bf16x3_t>(dy + p * ps + c, lo);
+        atomicAdd(&db[c], s);
+    }
+}
 
 extern "C" int yolo_bias_grad(const void* dy, float* db, long long npix, int C, long long pixel_stride, int dtype,
                               void* stream) {
     if (!dy || !db || npix <= 0 || C <= 0) return YOLO_EINVAL;
-    const long long ps = pixel_stride ? pixel_stride : C;
+    const long long ps = pixel_stride ? pixel_stride : (dtype == YOLO_BF16X3 ? dense_ps<bf16x3_t>(C) : C);
     const int ppb = 64;
     const unsigned nb = (unsigned)((npix + ppb - 1) / ppb);
-    if (dtype == YOLO_BF16)
+    if (dtype == YOLO_BF16X3) {
+        // (rows of a dense split tensor or of a wider one with the same planes: lo offset round_up(C, 32))
+        const int lo = dense_lo<bf16x3_t>(C);
+        if (ps < lo + C) return YOLO_EINVAL;
+        YOLO_LAUNCH(bias_grad_split_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const bf16x3_t*)dy, db, C, npix, ps, lo, ppb);
+    } else if (dtype == YOLO_BF16)
         YOLO_LAUNCH(bias_grad_kernel<bf16_t>, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, db, C, npix, ps, ppb);
     else if (dtype == YOLO_F32)
         YOLO_LAUNCH(bias_grad_kernel<float>, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const float*)dy, db, C, npix, ps, ppb);
@@ -1356,12 +1645,27 @@ __global__ void gather_rows_kernel(const float* __restrict__ src, T* __restrict_
     store1<T>(dst + i, c < C ? src[b * src_batch_stride + r * ps + c] : 0.f);
 }
 
+// split form: dst rows are dense split rows of Cpad channels (pixel stride 2 * round_up(Cpad, 32)); the pad beyond Cpad is not written
+__global__ void gather_rows_split_kernel(const float* __restrict__ src, bf16x3_t* __restrict__ dst, int C, int Cpad,
+                                         long long src_batch_stride, long long rows_per_batch, long long ps, long long total) {
+    const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int c = (int)(i % Cpad);
+    const long long row = i / Cpad;
+    const long long b = row / rows_per_batch, r = row - b * rows_per_batch;
+    store1s<bf16x3_t>(dst + row * dense_ps<bf16x3_t>(Cpad) + c, dense_lo<bf16x3_t>(Cpad),
+                      c < C ? src[b * src_batch_stride + r * ps + c] : 0.f);
+}
+
 extern "C" int yolo_gather_rows(const float* src, void* dst, int B, long long rows_per_batch, int C, int Cpad,
                                 long long src_batch_stride, long long src_row_stride, int dtype, void* stream) {
     if (!src || !dst || B <= 0 || rows_per_batch <= 0 || C <= 0 || Cpad < C) return YOLO_EINVAL;
     const long long total = (long long)B * rows_per_batch * Cpad;
     const unsigned nb = (unsigned)((total + 255) / 256);
-    if (dtype == YOLO_BF16)
+    if (dtype == YOLO_BF16X3)
+        YOLO_LAUNCH(gather_rows_split_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, src, (bf16x3_t*)dst, C, Cpad,
+                    src_batch_stride, rows_per_batch, src_row_stride, total);
+    else if (dtype == YOLO_BF16)
         YOLO_LAUNCH(gather_rows_kernel<bf16_t>, dim3(nb), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, C, Cpad,
                     src_batch_stride, rows_per_batch, src_row_stride, total);
     else if (dtype == YOLO_F32)
@@ -1394,6 +1698,29 @@ __global__ void dilate2_kernel(const T* __restrict__ dy, T* __restrict__ d, int 
     store8<T>(d + i * 8, v);
 }
 
+// split form: both planes of the C real channels are written (zeros off the even positions); the pad channels are not
+__global__ void dilate2_split_kernel(const uint16_t* __restrict__ dy, uint16_t* __restrict__ d, int H, int W, int Ho, int Wo,
+                                     int C8, long long ps, long long total8) {
+    const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (i >= total8) return;
+    const int c = (int)(i % C8);
+    long long p = i / C8;
+    const long long pix = p;
+    const int xx = (int)(p % W); p /= W;
+    const int yy = (int)(p % H);
+    const long long n = p / H;
+    const long long lo = ps / 2;
+    uint4 h = make_uint4(0, 0, 0, 0), l = h;
+    if (!(yy & 1) && !(xx & 1) && (yy >> 1) < Ho && (xx >> 1) < Wo) {
+        const uint16_t* s = dy + ((n * Ho + (yy >> 1)) * Wo + (xx >> 1)) * ps + c * 8;
+        h = *(const uint4*)s;
+        l = *(const uint4*)(s + lo);
+    }
+    uint16_t* o = d + pix * ps + c * 8;
+    *(uint4*)o = h;
+    *(uint4*)(o + lo) = l;
+}
+
 extern "C" int yolo_dilate2x(const void* dy, void* d, int N, int H, int W, int Ho, int Wo, int C, int dtype,
                              void* stream) {
     if (!dy || !d || N <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || C <= 0) return YOLO_EINVAL;
@@ -1401,7 +1728,10 @@ extern "C" int yolo_dilate2x(const void* dy, void* d, int N, int H, int W, int H
     if (C % 8) return YOLO_EUNSUPPORTED;
     const long long total8 = (long long)N * H * W * (C / 8);
     const unsigned nb = (unsigned)((total8 + 255) / 256);
-    if (dtype == YOLO_BF16)
+    if (dtype == YOLO_BF16X3)
+        YOLO_LAUNCH(dilate2_split_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)dy, (uint16_t*)d, H, W, Ho,
+                    Wo, C / 8, dense_ps<bf16x3_t>(C), total8);
+    else if (dtype == YOLO_BF16)
         YOLO_LAUNCH(dilate2_kernel<bf16_t>, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, (bf16_t*)d, H, W, Ho, Wo, C / 8, total8);
     else if (dtype == YOLO_F32)
         YOLO_LAUNCH(dilate2_kernel<float>, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const float*)dy, (float*)d, H, W, Ho, Wo, C / 8, total8);
@@ -1439,12 +1769,47 @@ __global__ void upcat_bwd_kernel(const T* __restrict__ dcat, T* __restrict__ dup
     }
 }
 
+// split form: dense split dcat (C1 + C2 channels), dup (C1) and droute (C2); sums and accumulations in fp32, stored as pairs
+__global__ void upcat_bwd_split_kernel(const bf16x3_t* __restrict__ dcat, bf16x3_t* __restrict__ dup, bf16x3_t* __restrict__ droute,
+                                       int H, int W, int C1, int C2, int acc_up, int acc_route, long long total_up,
+                                       long long total_route) {
+    const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    const int C = C1 + C2;
+    const long long psc = dense_ps<bf16x3_t>(C);
+    const int loc = dense_lo<bf16x3_t>(C);
+    if (i < total_up) {
+        const int c = (int)(i % C1);
+        long long p = i / C1;
+        const long long pix = p;
+        const int xx = (int)(p % (W / 2)); p /= (W / 2);
+        const int yy = (int)(p % (H / 2));
+        const long long n = p / (H / 2);
+        float s = 0.f;
+        for (int dy = 0; dy < 2; ++dy)
+            for (int dx = 0; dx < 2; ++dx) s += load1s<bf16x3_t>(dcat + ((n * H + 2 * yy + dy) * W + 2 * xx + dx) * psc + c, loc);
+        bf16x3_t* o = dup + pix * dense_ps<bf16x3_t>(C1) + c;
+        const int lo = dense_lo<bf16x3_t>(C1);
+        store1s<bf16x3_t>(o, lo, acc_up ? load1s<bf16x3_t>(o, lo) + s : s);
+    } else if (i < total_up + total_route) {
+        const long long j = i - total_up;
+        const int c = (int)(j % C2);
+        const long long p = j / C2;
+        const float v = load1s<bf16x3_t>(dcat + p * psc + C1 + c, loc);
+        bf16x3_t* o = droute + p * dense_ps<bf16x3_t>(C2) + c;
+        const int lo = dense_lo<bf16x3_t>(C2);
+        store1s<bf16x3_t>(o, lo, acc_route ? load1s<bf16x3_t>(o, lo) + v : v);
+    }
+}
+
 extern "C" int yolo_upsample2x_concat_bwd(const void* dcat, void* dup, void* droute, int N, int H, int W, int C1,
                                           int C2, int accumulate_up, int accumulate_route, int dtype, void* stream) {
     if (!dcat || !dup || !droute || N <= 0 || (H & 1) || (W & 1) || C1 <= 0 || C2 <= 0) return YOLO_EINVAL;
     const long long tu = (long long)N * (H / 2) * (W / 2) * C1, tr = (long long)N * H * W * C2;
     const unsigned nb = (unsigned)((tu + tr + 255) / 256);
-    if (dtype == YOLO_BF16)
+    if (dtype == YOLO_BF16X3)
+        YOLO_LAUNCH(upcat_bwd_split_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const bf16x3_t*)dcat, (bf16x3_t*)dup,
+                    (bf16x3_t*)droute, H, W, C1, C2, accumulate_up, accumulate_route, tu, tr);
+    else if (dtype == YOLO_BF16)
         YOLO_LAUNCH(upcat_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dcat, (bf16_t*)dup,
                     (bf16_t*)droute, H, W, C1, C2, accumulate_up, accumulate_route, tu, tr);
     else if (dtype == YOLO_F32)
@@ -1471,6 +1836,27 @@ extern "C" int yolo_add(const void* a, const void* b, void* y, long long n, int 
         YOLO_LAUNCH(add_kernel<float>, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const float*)a, (const float*)b, (float*)y, n);
     else
         return YOLO_EINVAL;
+    YOLO_LAUNCH_CHECK();
+    return YOLO_OK;
+}
+
+// split form: y = a + b over npix pixels of C channels of dense split tensors (a value's lo plane is round_up(C, 32) behind it,
+// which yolo_add's element count alone cannot locate)
+__global__ void add_split_kernel(const bf16x3_t* __restrict__ a, const bf16x3_t* __restrict__ b, bf16x3_t* __restrict__ y, int C,
+                                 long long total) {
+    const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long long p = i / C;
+    const int c = (int)(i - p * C);
+    const long long o = p * dense_ps<bf16x3_t>(C) + c;
+    const int lo = dense_lo<bf16x3_t>(C);
+    store1s<bf16x3_t>(y + o, lo, load1s<bf16x3_t>(a + o, lo) + load1s<bf16x3_t>(b + o, lo));
+}
+extern "C" int yolo_add_split(const void* a, const void* b, void* y, long long npix, int C, int dtype, void* stream) {
+    if (!a || !b || !y || npix <= 0 || C <= 0 || dtype != YOLO_BF16X3) return YOLO_EINVAL;
+    const long long total = npix * C;
+    YOLO_LAUNCH(add_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16x3_t*)a,
+                (const bf16x3_t*)b, (bf16x3_t*)y, C, total);
     YOLO_LAUNCH_CHECK();
     return YOLO_OK;
 }

@@ -12,7 +12,7 @@ CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('YOLO_AMD_LIB') or os.path.join(CSRC, 'libyolo_amd.so')   # override: experiment builds
 
 F32, BF16, F16, BF16X3, F16X3 = 0, 1, 2, 3, 4
-ABI_VERSION = 4            # include/yolo_amd.h: YOLO_ABI_VERSION (the struct layouts below are revision 4's)
+ABI_VERSION = 5            # include/yolo_amd.h: YOLO_ABI_VERSION (the struct layouts below are unchanged since revision 4)
 OK, EINVAL, EUNSUPPORTED = 0, -1, -2
 
 
@@ -105,11 +105,14 @@ SIGNATURES = {
     'yolo_conv_wgrad_workspace_bytes': (_ll, [_i, _i, _i, _i]),
     'yolo_conv_wgrad': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _ll, _i, _vp, _vp]),
     'yolo_conv_wgrad_algo': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _ll, _i, _vp, _i, _vp]),
+    'yolo_conv_wgrad_split_workspace_bytes': (_ll, [_i, _i, _i, _i]),
+    'yolo_conv_wgrad_split': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _ll, _ll, _i, _vp, _i, _vp]),
     'yolo_bias_grad': (_i, [_vp, _vp, _ll, _i, _ll, _i, _vp]),
     'yolo_gather_rows': (_i, [_vp, _vp, _i, _ll, _i, _i, _ll, _ll, _i, _vp]),
     'yolo_dilate2x': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'yolo_upsample2x_concat_bwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'yolo_add': (_i, [_vp, _vp, _vp, _ll, _i, _vp]),
+    'yolo_add_split': (_i, [_vp, _vp, _vp, _ll, _i, _i, _vp]),
     'yolo_assign_targets': (_i, [_vp, _vp, _vp, _i, _i, _i, C.POINTER(GridDesc), _vp]),
     'yolo_loss_fwd_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(C.c_float), _f, _f, _vp]),
     'yolo_assign_targets_lp': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp]),

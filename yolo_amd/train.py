@@ -4,7 +4,8 @@ sum(losses), gradient all-reduce over ranks and the MXNet Adam update of trainer
 
 fp32 parity path: every op is a HIP kernel from libyolo_amd.so (train.hip, loss.hip and the forward conv
 kernels re-used for the data gradient on flipped weights); torch owns memory, the stream and the
-process group only.  One process per GPU; BN statistics stay local to the GPU (no SyncBN,
+process group only.  dtype 'bf16x3' (the split-bf16 path, include/yolo_amd.h YOLO_BF16X3) runs the same graph on (hi, lo) pairs:
+the fp32 arithmetic of the reference to ~16 significant bits at the bf16 MFMA rate.  One process per GPU; BN statistics stay local to the GPU (no SyncBN,
 car/YOLO.py:94-96).
 """
 import os
@@ -24,10 +25,11 @@ LP_DEFAULT_SCALE = {'LP_score': 0.1, 'LP_xy': 10.0, 'LP_z': 1.0, 'LP_r': 0.1, 'L
 
 class _T(object):
     """An activation of the training graph: forward value + (lazily) its gradient."""
-    __slots__ = ('val', 'shape', 'grad', 'ready', 'ngot')
+    __slots__ = ('val', 'shape', 'grad', 'ready', 'ngot', 'gbuf')
 
-    def __init__(self, val, shape):
-        self.val, self.shape, self.grad, self.ready, self.ngot = val, shape, None, False, 0
+    def __init__(self, val, shape, gbuf=None):
+        # gbuf (split path): the plan-owned buffer of the gradient's first contribution (zeroed pads, never re-allocated)
+        self.val, self.shape, self.grad, self.ready, self.ngot, self.gbuf = val, shape, None, False, 0, gbuf
 
 
 class Trainer(object):
@@ -36,13 +38,18 @@ class Trainer(object):
                  lp_positive_weight=1.0, lp_negative_weight=0.1, grad_exchange='f32', grad_buckets=4):
         # grad_exchange / grad_buckets (N > 1): the dtype the gradient buckets travel in ('f32' = the reference's KVStore sum;
         # 'bf16' halves the bytes per xGMI link, parallel.GradBuckets) and how many buckets the 492 MB buffer is cut into
-        # dtype of activations and activation gradients: 'f32' (parity path) or 'bf16' (MFMA bf16 convolutions,
-        # transposing-read weight gradient); master weights, weight gradients, BN statistics and Adam are fp32.
+        # dtype of activations and activation gradients: 'f32' (parity path), 'bf16' (MFMA bf16 convolutions,
+        # transposing-read weight gradient) or 'bf16x3' (split pairs: the bf16x3 inference kernels for the forward and data
+        # gradient, yolo_conv_wgrad_split for the weight gradient); master weights, weight gradients, BN statistics and Adam are fp32.
         self.net, self.size = net, (int(size[0]), int(size[1]))
         self.tdt = torch.float32 if net.dtype == 'f32' else torch.bfloat16
-        if net.dtype not in ('f32', 'bf16'):
-            raise L.YoloError("Trainer: dtype %r is inference only (the training kernels take 'f32' | 'bf16')" % (net.dtype,))
-        self.ldt = L.F32 if net.dtype == 'f32' else L.BF16
+        if net.dtype not in ('f32', 'bf16', 'bf16x3'):
+            raise L.YoloError("Trainer: dtype %r is inference only (the training kernels take 'f32' | 'bf16' | 'bf16x3')" % (net.dtype,))
+        self.ldt = {'f32': L.F32, 'bf16': L.BF16, 'bf16x3': L.BF16X3}[net.dtype]
+        self.split = self.ldt == L.BF16X3
+        # the measured data- / weight-gradient choices are keyed by layer shape; a plan file's keys carry no dtype and hold bf16
+        # choices, so every other dtype keys its own choices by its name (a bf16 algo id would be refused on an f32 or split conv)
+        self._key_tag = () if self.ldt == L.BF16 else (net.dtype,)
         self.lib, self.dev = net._lib, net.device
         self.scale = dict(DEFAULT_SCALE if scale is None else scale)
         self.lr, self.b1, self.b2, self.eps = learning_rate, beta1, beta2, eps
@@ -103,7 +110,8 @@ class Trainer(object):
         self.probe = None         # a list: _backward appends (family, layer, elements, start event, end event) per BatchNorm backward call
         self._bn3 = bool(L.lab_knob('YOLO_TRAIN_BN3'))      # (the knob: separate finalize launches, for A/B runs)
         self.ws = torch.zeros(2 * cmax, dtype=torch.float64, device=self.dev)
-        wsb = max(self.lib.yolo_conv_wgrad_workspace_bytes(max(c.cin, 8), c.cout, c.k, self.ldt) for c in g.convs())
+        wsf = self.lib.yolo_conv_wgrad_split_workspace_bytes if self.split else self.lib.yolo_conv_wgrad_workspace_bytes
+        wsb = max(wsf(max(c.cin, 8), c.cout, c.k, self.ldt) for c in g.convs())
         self.wg_ws = torch.zeros(max(wsb, 16), dtype=torch.uint8, device=self.dev)       # (kept zeroed by the library)
         # weight gradients run on a side stream: they are off the backward pass's critical path (dy -> data gradient ->
         # previous layer's BN backward) and MFMA-bound, while the BN passes they overlap are HBM-bound
@@ -135,6 +143,9 @@ class Trainer(object):
         """Forward and data-gradient weight images of every conv, re-packed after each update in ONE launch
         (yolo_pack_conv_weights_batch) over a device-resident table built on first use."""
         lib, st = self.lib, L.stream_ptr()
+        if self.split:
+            self._repack_split()
+            return
         if not self._prep:
             items = np.zeros(0, dtype=[('w', '<u8'), ('packed', '<u8'), ('cout', '<i4'), ('cin', '<i4'), ('k', '<i4'), ('dgrad', '<i4')])
             recs, first = [], [0]
@@ -187,8 +198,56 @@ class Trainer(object):
             if not c.bn:
                 self._prep[c.name][3][:c.cout].copy_(self.pview[c.name + '.bias'])
 
+    def _repack_split(self):
+        """Split path: the forward and data-gradient images of every conv, per conv (yolo_pack_batch_blocks has no split form).
+        A split image needs Cin % 8 == 0: the data-gradient image of an output conv whose Cout is not a multiple of 8 is packed
+        from a copy of its weights with zero rows up to the padded gradient rows it runs on."""
+        lib, st = self.lib, L.stream_ptr()
+        if not self._prep:
+            self._split_items = []
+            for c in self.net.graph.convs():
+                w = self.pview[c.name + '.weight']
+                cof = c.cout if c.cout % 8 == 0 else (c.cout + 7) // 8 * 8
+                wpad = torch.zeros((cof, c.cin, c.k, c.k), dtype=torch.float32, device=self.dev) if cof != c.cout else None
+                # (the 3-channel stem: its forward image over the 8-channel image copy -- used only where the split stem kernel
+                #  does not take the layer --, no data-gradient image: nothing is behind the stem)
+                cip = c.cin if c.cin % 8 == 0 else (c.cin + 7) // 8 * 8
+                win = torch.zeros((c.cout, cip, c.k, c.k), dtype=torch.float32, device=self.dev) if cip != c.cin else None
+                wp = torch.zeros(lib.yolo_packed_weight_bytes(c.cout, cip, c.k, self.ldt), dtype=torch.uint8, device=self.dev)
+                wd = (torch.zeros(lib.yolo_packed_weight_bytes(c.cin, cof, c.k, self.ldt), dtype=torch.uint8, device=self.dev)
+                      if win is None else None)
+                cp = lib.yolo_padded_channels(max(c.cout, c.cin))
+                ones = torch.zeros(cp, dtype=torch.float32, device=self.dev); ones[:max(c.cout, c.cin)] = 1.0
+                bias = torch.zeros(cp, dtype=torch.float32, device=self.dev)
+                self._prep[c.name] = (wp, wd, ones, bias, torch.zeros(cp, dtype=torch.float32, device=self.dev))
+                self._split_items.append((c, w, wpad, cof, win, cip, wp, wd))
+        for c, w, wpad, cof, win, cip, wp, wd in self._split_items:
+            if win is not None:
+                win[:, :c.cin].copy_(w)
+                L.check(lib.yolo_pack_conv_weights(L.ptr(win), L.ptr(wp), c.cout, cip, c.k, self.ldt, st), 'pack ' + c.name)
+                continue
+            L.check(lib.yolo_pack_conv_weights(L.ptr(w), L.ptr(wp), c.cout, c.cin, c.k, self.ldt, st), 'pack ' + c.name)
+            src = w
+            if wpad is not None:
+                wpad[:c.cout].copy_(w)
+                src = wpad
+            L.check(lib.yolo_pack_conv_weights_dgrad(L.ptr(src), L.ptr(wd), cof, c.cin, c.k, self.ldt, st), 'pack dgrad ' + c.name)
+        for c in self.net.graph.convs():
+            if not c.bn:
+                self._prep[c.name][3][:c.cout].copy_(self.pview[c.name + '.bias'])
+
     # ---- plan ---------------------------------------------------------------------------------------------
+    def _buf(self, shape):
+        """An activation-shaped buffer (N, H, W, C).  Split path: the dense pair storage (N, H, W, 2, round_up(C, 32)), ZEROED --
+        the kernels never write the pad channels, which the convolutions read as operands of zero weights."""
+        if not self.split:
+            return torch.empty(shape, dtype=self.tdt, device=self.dev)
+        cp = -(-shape[-1] // 32) * 32
+        return torch.zeros(tuple(shape[:-1]) + (2, cp), dtype=self.tdt, device=self.dev)
+
     def _new(self, shape):
+        if self.split:
+            return _T(self._buf(shape), tuple(shape), gbuf=self._buf(shape))
         return _T(torch.empty(shape, dtype=self.tdt, device=self.dev), tuple(shape))
 
     def _conv_desc(self, x, xshape, wp, scale, bias, y, cin, cout, k, stride, residual=None, out_f32=0, y_bs=0, y_ps=0):
@@ -212,7 +271,8 @@ class Trainer(object):
         P = type('Plan', (), {})()
         P.fwd, P.tensors = [], []
         P.stats_floats = 0
-        P.x8 = self._new((B, H, W, 8))
+        # (the 8-channel image copy: the stem's input, which receives no gradient -- no gradient buffer on the split path)
+        P.x8 = _T(self._buf((B, H, W, 8)), (B, H, W, 8)) if self.split else self._new((B, H, W, 8))
 
         def conv_bn(c, xin, residual=None):
             N, Hh, Ww, Cc = xin.shape
@@ -225,6 +285,11 @@ class Trainer(object):
             d = self._conv_desc(xin.val, xin.shape, wp, ident[0], ident[1], yraw.val, Cc, c.cout, c.k, c.stride)
             self._tune(d)
             op = dict(kind='conv_bn', c=c, x=xin, yraw=yraw, z=z, mean=mean, invstd=invstd, res=residual, desc=d, srows=0, brows=0)
+            if self.split:
+                # the plan owns every gradient buffer of the split path: d(loss)/d(yraw) and, for a stride-2 conv, its dilated copy
+                op['dy'] = yraw.gbuf
+                if c.stride == 2:
+                    op['dil'] = self._buf((N, Hh, Ww, c.cout))
             # (small maps keep the reduction pass of their own: it costs nothing there, and its sums are taken around a value of the
             #  channel -- the epilogue's plain fp32 partial sums lose digits when a few nearly equal values make mean^2 >> variance)
             if self._fuse_fwd and not (c is g.stem) and N * ho * wo >= 4096 and self._pipe_kernel(d):
@@ -273,7 +338,7 @@ class Trainer(object):
                 cpad = (lc.cout + 7) // 8 * 8
                 P.fwd.append(dict(kind='out', c=lc, x=t, desc=d, hw=hw_lp, cpad=cpad,
                                   src=(P.dlp.data_ptr(), hw_lp * lc.cout, lc.cout),
-                                  dyp=torch.empty((B * hw_lp, cpad), dtype=self.tdt, device=self.dev)))
+                                  dyp=self._buf((B * hw_lp, cpad))))
                 P.lp_hw = (t.shape[1], t.shape[2])
             for c in body:
                 x = conv_bn(c, x)
@@ -287,7 +352,7 @@ class Trainer(object):
             cpad = (outc.cout + 7) // 8 * 8
             P.fwd.append(dict(kind='out', c=outc, x=t, desc=d, hw=hw[k], cpad=cpad,
                               src=(P.dmerged.data_ptr() + offs[k] * AC * 4, tot * AC, AC),
-                              dyp=torch.empty((B * hw[k], cpad), dtype=self.tdt, device=self.dev)))
+                              dyp=self._buf((B * hw[k], cpad))))
             if i >= len(g.heads) - 1:
                 break
             x = conv_bn(g.transitions[i], route)
@@ -295,6 +360,7 @@ class Trainer(object):
             cat = self._new((r.shape[0], r.shape[1], r.shape[2], x.shape[3] + r.shape[3]))
             P.fwd.append(dict(kind='upcat', up=x, route=r, cat=cat))
             x = cat
+        P.dil = {op['c'].name: op['dil'] for op in P.fwd if 'dil' in op}      # (split path: the plan-owned dilated gradients)
         # forward statistics partials: one buffer, consumed by the BatchNorm call right behind each convolution
         P.stats_f = torch.empty(max(P.stats_floats, 4), dtype=torch.float32, device=self.dev)
         for op in P.fwd:
@@ -356,7 +422,16 @@ class Trainer(object):
                     L.check(lib.yolo_stem_conv_fwd(images.data_ptr(), L.ptr(self.pview[c.name + '.weight']), L.ptr(ones),
                                                    L.ptr(zeros), L.ptr(y.val), B, H, W, 3, c.cout, self.ldt, 1.0, st), 'stem')
                 else:
-                    L.check(lib.yolo_conv_fwd(C.byref(op['desc']), st), 'conv ' + c.name)
+                    rc = L.EUNSUPPORTED
+                    if c is g.stem and self.split and c.cin == 3:
+                        # the split stem kernel of the inference path on the NCHW image (identity scale/bias, linear): raw y;
+                        # a stem it does not take (Cout) runs as a convolution of the 8-channel image copy
+                        rc = lib.yolo_stem_conv_fwd(images.data_ptr(), L.ptr(self.pview[c.name + '.weight']), L.ptr(self._prep[c.name][2]),
+                                                    L.ptr(self._prep[c.name][4]), L.ptr(y.val), B, H, W, 3, c.cout, self.ldt, 1.0, st)
+                        if rc != L.EUNSUPPORTED:
+                            L.check(rc, 'stem')
+                    if rc == L.EUNSUPPORTED:
+                        L.check(lib.yolo_conv_fwd(C.byref(op['desc']), st), 'conv ' + c.name)
                 npix = y.shape[0] * y.shape[1] * y.shape[2]
                 p = self.net.params
                 if self._bn3:
@@ -393,6 +468,9 @@ class Trainer(object):
         t.ngot += 1
         if not t.ready:
             t.grad, t.ready = src, True
+        elif self.split:
+            N, Hh, Ww, Cc = t.shape
+            L.check(self.lib.yolo_add_split(L.ptr(t.grad), L.ptr(src), L.ptr(t.grad), N * Hh * Ww, Cc, self.ldt, L.stream_ptr()), 'add')
         else:
             L.check(self.lib.yolo_add(L.ptr(t.grad), L.ptr(src), L.ptr(t.grad), src.numel(), self.ldt, L.stream_ptr()), 'add')
 
@@ -431,13 +509,13 @@ class Trainer(object):
                 L.check(rc, 'dgrad_s2 ' + c.name)
             del self._prep_s2[c.name]              # no variant fits this shape: the dilated form from now on
         if c.stride == 2:
-            dil = torch.empty((N, Hh, Ww, cin_of_dy), dtype=self.tdt, device=self.dev)
+            dil = self._P.dil[c.name] if self.split else torch.empty((N, Hh, Ww, cin_of_dy), dtype=self.tdt, device=self.dev)
             L.check(lib.yolo_dilate2x(L.ptr(dy), L.ptr(dil), N, Hh, Ww, dy_shape[1], dy_shape[2], cin_of_dy, self.ldt, st), 'dilate')
             src, sshape = dil, (N, Hh, Ww, cin_of_dy)
         else:
             src, sshape = dy, dy_shape
         if not xin.ready:
-            out = torch.empty(xin.shape, dtype=self.tdt, device=self.dev)
+            out = xin.gbuf if self.split else torch.empty(xin.shape, dtype=self.tdt, device=self.dev)
             resid = None
         else:
             out, resid = xin.grad, xin.grad
@@ -448,10 +526,10 @@ class Trainer(object):
         P = self._P
         prod = P.prod.get(id(xin)) if (self._fuse_bwd and c.stride == 1 and xin.ngot + 1 == P.nuse.get(id(xin), 0)) else None
         if getattr(self.net, 'tune', None) == 'measure':
-            key = (sshape, cin_of_dy, Cx, c.k, resid is not None)
+            key = self._key_tag + (sshape, cin_of_dy, Cx, c.k, resid is not None)
             if key not in self._dgrad_algo:
                 # time the variants on scratch outputs: the real `out` may already hold an accumulated gradient
-                scratch = torch.zeros(xin.shape, dtype=self.tdt, device=self.dev)
+                scratch = self._buf(xin.shape) if self.split else torch.zeros(xin.shape, dtype=self.tdt, device=self.dev)
                 dm = self._conv_desc(src, sshape, wd, ones, zeros, scratch, cin_of_dy, Cx, c.k, 1,
                                      residual=scratch if resid is not None else None)
                 self._dgrad_algo[key] = self.net._measure_algo(dm)
@@ -485,14 +563,16 @@ class Trainer(object):
         """yolo_conv_wgrad_algo id for conv c: 0 (the library's choice) unless the net was built with tune='measure' -- then the
         fastest of the kernels that take the shape, timed once per layer shape on a scratch gradient (the 8-wave row walk wins
         on two D53 shapes, the 16-column walker on the 13x13 ones, ...)."""
-        if getattr(self.net, 'tune', None) != 'measure' or self.ldt != L.BF16 or L.lab_knob('YOLO_TRAIN_NO_WGRAD_TUNE'):
+        if getattr(self.net, 'tune', None) != 'measure' or self.ldt == L.F32 or L.lab_knob('YOLO_TRAIN_NO_WGRAD_TUNE'):
             return 0
         N, Hh, Ww, Cx = xin.shape
-        key = (N, Hh, Ww, Cx, c.cout, c.k, c.stride)
+        key = self._key_tag + (N, Hh, Ww, Cx, c.cout, c.k, c.stride)
         if key not in self._wgrad_algo and not getattr(self.net, 'measure_live', True):
             return 0                                      # (tune='plan', a shape the plan does not hold: the library's choice)
         if key not in self._wgrad_algo:
             cands = (0, 2, 3, 4) if (c.k == 3 and c.stride == 1) else (0, 1, 5) if c.k == 1 else (0,)
+            if self.split:
+                cands = (0, 1, 2)                     # yolo_conv_wgrad_split: the library's choice, 64 x 64, 128 x 128 tiles
             best, best_t = 0, float('inf')
             if len(cands) > 1:
                 lib, st = self.lib, L.stream_ptr()
@@ -503,6 +583,9 @@ class Trainer(object):
                 scratch = torch.zeros((c.cout, Cx, c.k, c.k), dtype=torch.float32, device=self.dev)
                 call = lambda a: lib.yolo_conv_wgrad_algo(L.ptr(dy), L.ptr(xin.val), L.ptr(scratch), N, Hh, Ww, Cx, c.cout, c.k,
                                                           c.stride, 0, self.ldt, L.ptr(self.wg_ws), a, st)
+                if self.split:
+                    call = lambda a: lib.yolo_conv_wgrad_split(L.ptr(dy), L.ptr(xin.val), L.ptr(scratch), N, Hh, Ww, Cx, c.cout,
+                                                               c.k, c.stride, 0, 0, self.ldt, L.ptr(self.wg_ws), a, st)
                 for a in cands:
                     if call(a) != 0:
                         continue
@@ -559,7 +642,8 @@ class Trainer(object):
     def _backward(self, P, exchange=True, capture=None):
         """capture: optional dict that receives, per conv name, the gradient w.r.t. the layer output as the layer saw it
         (`dz`, a copy: the buffer is re-used as the residual branch's gradient) and w.r.t. the raw convolution output
-        (`dy`) -- parity tests re-derive every gradient of the step from them (tests/test_gpu_configs.py)."""
+        (`dy`) -- parity tests re-derive every gradient of the step from them (tests/test_gpu_configs.py).  Split path: both
+        are fp32 (N, H, W, C) copies of the values hi + lo, not the (N, H, W, 2, Cp) pair buffers the step re-uses."""
         lib, st = self.lib, L.stream_ptr()
         g = self.net.graph
         self.gflat.zero_()
@@ -582,18 +666,27 @@ class Trainer(object):
                 hw, cpad = op['hw'], op['cpad']
                 src, src_bs, src_ps = op['src']            # this output's slice of d(loss)/d(logits), fp32
                 L.check(lib.yolo_gather_rows(src, L.ptr(op['dyp']), B, hw, c.cout, cpad, src_bs, src_ps, self.ldt, st), 'gather')
-                L.check(lib.yolo_bias_grad(L.ptr(op['dyp']), L.ptr(self.gview[c.name + '.bias']), B * hw, c.cout, cpad, self.ldt, st), 'db')
+                L.check(lib.yolo_bias_grad(L.ptr(op['dyp']), L.ptr(self.gview[c.name + '.bias']), B * hw, c.cout,
+                                           0 if self.split else cpad, self.ldt, st), 'db')
                 N, Hh, Ww, Cx = xin.shape
-                self._wgrad(op['dyp'], [c.name + '.weight', c.name + '.bias'], lambda s_, c=c, op=op, xin=xin, N=N, Hh=Hh, Ww=Ww, Cx=Cx, cpad=cpad: L.check(
-                    lib.yolo_conv_wgrad(L.ptr(op['dyp']), L.ptr(xin.val), L.ptr(self.gview[c.name + '.weight']),
-                                        N, Hh, Ww, Cx, c.cout, 1, 1, cpad, self.ldt, L.ptr(self.wg_ws), s_), 'wgrad out'), tag='out')
+                if self.split:
+                    # (dense split rows of cpad channels: planes of round_up(cpad, 32))
+                    scp = -(-cpad // 32) * 32
+                    launch = lambda s_, c=c, op=op, xin=xin, N=N, Hh=Hh, Ww=Ww, Cx=Cx, scp=scp: L.check(
+                        lib.yolo_conv_wgrad_split(L.ptr(op['dyp']), L.ptr(xin.val), L.ptr(self.gview[c.name + '.weight']), N, Hh,
+                                                  Ww, Cx, c.cout, 1, 1, 2 * scp, scp, self.ldt, L.ptr(self.wg_ws), 0, s_), 'wgrad out')
+                else:
+                    launch = lambda s_, c=c, op=op, xin=xin, N=N, Hh=Hh, Ww=Ww, Cx=Cx, cpad=cpad: L.check(
+                        lib.yolo_conv_wgrad(L.ptr(op['dyp']), L.ptr(xin.val), L.ptr(self.gview[c.name + '.weight']),
+                                            N, Hh, Ww, Cx, c.cout, 1, 1, cpad, self.ldt, L.ptr(self.wg_ws), s_), 'wgrad out')
+                self._wgrad(op['dyp'], [c.name + '.weight', c.name + '.bias'], launch, tag='out')
                 self._dgrad(c, op['dyp'], (N, Hh, Ww, cpad), xin, cpad)
             elif kind == 'upcat':
                 up, r, cat = op['up'], op['route'], op['cat']
                 if not up.ready:
-                    up.grad = torch.empty(up.shape, dtype=self.tdt, device=self.dev)
+                    up.grad = up.gbuf if self.split else torch.empty(up.shape, dtype=self.tdt, device=self.dev)
                 if not r.ready:
-                    r.grad = torch.empty(r.shape, dtype=self.tdt, device=self.dev)
+                    r.grad = r.gbuf if self.split else torch.empty(r.shape, dtype=self.tdt, device=self.dev)
                 L.check(lib.yolo_upsample2x_concat_bwd(L.ptr(cat.grad), L.ptr(up.grad), L.ptr(r.grad), r.shape[0], r.shape[1],
                                                        r.shape[2], up.shape[3], r.shape[3], int(up.ready), int(r.ready), self.ldt, st),
                         'upcat bwd')
@@ -605,8 +698,8 @@ class Trainer(object):
                 dz = z.grad
                 npix = y.shape[0] * y.shape[1] * y.shape[2]
                 p = self.net.params
-                dy = torch.empty(y.shape, dtype=self.tdt, device=self.dev)
-                if capture is not None and capture.get('_poison'):
+                dy = op['dy'] if self.split else torch.empty(y.shape, dtype=self.tdt, device=self.dev)
+                if capture is not None and capture.get('_poison') and not self.split:
                     dy.fill_(float('nan'))          # (diagnostics: an element the kernel does not write must show)
                 if self._bn3:
                     L.check(lib.yolo_bn_train_bwd(L.ptr(dz), L.ptr(y.val), L.ptr(op['mean']), L.ptr(op['invstd']),
@@ -637,7 +730,13 @@ class Trainer(object):
                         e1.record()
                         pr.append(('bn_bwd', c.name, npix * c.cout, e0, e1))
                 if capture is not None:
-                    capture[c.name] = dict(dz=dz.clone(), dy=dy)
+                    if self.split:
+                        # the values hi + lo as fp32 (N, H, W, C) copies: the split buffers are plan-owned, and the next step
+                        # overwrites them
+                        plain = lambda t, C_=c.cout: t[..., 0, :C_].float() + t[..., 1, :C_].float()
+                        capture[c.name] = dict(dz=plain(dz), dy=plain(dy))
+                    else:
+                        capture[c.name] = dict(dz=dz.clone(), dy=dy)
                 if op['res'] is not None:
                     self._accum(op['res'], dz)          # the residual branch receives dz unchanged
                 N, Hh, Ww, Cx = xin.shape
@@ -646,16 +745,26 @@ class Trainer(object):
                     def stem_wgrad(s_, c=c, dy=dy, xin=xin, N=N, Hh=Hh, Ww=Ww):
                         # (torch ops below run on the stream _wgrad has made current)
                         dw8 = torch.zeros((c.cout, 8, 3, 3), dtype=torch.float32, device=self.dev)
-                        L.check(lib.yolo_conv_wgrad(L.ptr(dy), L.ptr(xin.val), L.ptr(dw8), N, Hh, Ww, 8, c.cout, 3, 1, 0, self.ldt,
-                                                    L.ptr(self.wg_ws), s_), 'wgrad stem')
+                        if self.split:
+                            # (x: the 8-channel split copy of the image yolo_nchw_to_nhwc wrote in the forward pass)
+                            L.check(lib.yolo_conv_wgrad_split(L.ptr(dy), L.ptr(xin.val), L.ptr(dw8), N, Hh, Ww, 8, c.cout, 3, 1, 0, 0,
+                                                              self.ldt, L.ptr(self.wg_ws), 0, s_), 'wgrad stem')
+                        else:
+                            L.check(lib.yolo_conv_wgrad(L.ptr(dy), L.ptr(xin.val), L.ptr(dw8), N, Hh, Ww, 8, c.cout, 3, 1, 0, self.ldt,
+                                                        L.ptr(self.wg_ws), s_), 'wgrad stem')
                         self.gview[c.name + '.weight'].copy_(dw8[:, :3])
                     self._wgrad(dy, names, stem_wgrad, tag='stem')
                 else:
                     wa = self._wgrad_algo_for(c, dy, xin)
-                    self._wgrad(dy, names, lambda s_, c=c, dy=dy, xin=xin, N=N, Hh=Hh, Ww=Ww, Cx=Cx, wa=wa: L.check(
-                        lib.yolo_conv_wgrad_algo(L.ptr(dy), L.ptr(xin.val), L.ptr(self.gview[c.name + '.weight']), N, Hh, Ww,
-                                                 Cx, c.cout, c.k, c.stride, 0, self.ldt, L.ptr(self.wg_ws), wa, s_), 'wgrad ' + c.name),
-                                tag=self._wgrad_tag(c, Cx))
+                    if self.split:
+                        launch = lambda s_, c=c, dy=dy, xin=xin, N=N, Hh=Hh, Ww=Ww, Cx=Cx, wa=wa: L.check(
+                            lib.yolo_conv_wgrad_split(L.ptr(dy), L.ptr(xin.val), L.ptr(self.gview[c.name + '.weight']), N, Hh, Ww,
+                                                      Cx, c.cout, c.k, c.stride, 0, 0, self.ldt, L.ptr(self.wg_ws), wa, s_), 'wgrad ' + c.name)
+                    else:
+                        launch = lambda s_, c=c, dy=dy, xin=xin, N=N, Hh=Hh, Ww=Ww, Cx=Cx, wa=wa: L.check(
+                            lib.yolo_conv_wgrad_algo(L.ptr(dy), L.ptr(xin.val), L.ptr(self.gview[c.name + '.weight']), N, Hh, Ww,
+                                                     Cx, c.cout, c.k, c.stride, 0, self.ldt, L.ptr(self.wg_ws), wa, s_), 'wgrad ' + c.name)
+                    self._wgrad(dy, names, launch, tag=self._wgrad_tag(c, Cx))
                     self._dgrad(c, dy, y.shape, xin, c.cout)
         self._flush_wgrad()
         if self._overlap:
