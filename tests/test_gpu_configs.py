@@ -41,7 +41,7 @@ def _kink_flips(dy, dy_ref, a_ref, tol, a_impl=None, frac=2e-5):
     the kink's factor.  Legitimate only for elements whose BatchNorm output is within rounding of zero -- checked -- and
     only for a handful of them.
 
-    a_impl: the BatchNorm output as the implementation's fp32 arithmetic evaluates it (train.hip: xh = (y - mean) * invstd;
+    a_impl: the BatchNorm output as the implementation's fp32 arithmetic evaluates it (bn_train.hip: xh = (y - mean) * invstd;
     a = gamma * xh + beta, no contraction) -- the branch decisions are then read off it directly.  Without it only the
     elements whose dy is off by more than `tol` are found: a flipped element with a smaller dz stayed in the reference's
     sums (round 4: one such element, 1.9 % of the largest dy, put dbeta of stages.2.res.7.c1 -- a sum that cancels to

@@ -28,8 +28,8 @@ def test_split_training_entries_declared_and_bound():
 
 SPLIT_KERNELS = [r'wgrad_split_kernel<1, 1>', r'wgrad_split_kernel<2, 2>', r'bn_reduce_kernel<bf16x3_t, 0>',
                  r'bn_reduce_kernel<bf16x3_t, 1>', r'bn_apply_kernel<bf16x3_t, 0, 1>', r'bn_apply_kernel<bf16x3_t, 1, 1>',
-                 r'bias_grad_split_kernel', r'gather_rows_split_kernel', r'dilate2_split_kernel', r'upcat_bwd_split_kernel',
-                 r'add_split_kernel', r'upsample_concat_split_kernel', r'nchw_to_nhwc_split_kernel']
+                 r'bias_grad_kernel<bf16x3_t>', r'gather_rows_kernel<bf16x3_t>', r'dilate2_kernel<bf16x3_t>', r'upcat_bwd_kernel<bf16x3_t>',
+                 r'add_kernel<bf16x3_t>', r'upsample_concat_kernel<2>', r'nchw_to_nhwc_kernel<bf16x3_t, 8>']
 
 
 def test_split_training_kernels_have_no_scratch(tmp_path):

@@ -118,6 +118,14 @@ template <> __device__ __forceinline__ f32x16 mfma16<f16x3_t>(const uint4& a, co
 template <typename T> struct IsBf16 { static constexpr bool value = false; };
 template <> struct IsBf16<bf16_t> { static constexpr bool value = true; };
 
+// dtype code -> element tag, for the entry points: f(T{}) for the one of Ts... whose code `dtype` is (T = decltype of the lambda's
+// argument), YOLO_EINVAL for every other code -- each entry point lists exactly the types it takes
+template <typename... Ts, typename F> static inline int dispatch_dtype(int dtype, F&& f) {
+    int rc = YOLO_EINVAL;
+    (void)((dtype == Elem<Ts>::dtype && ((rc = f(Ts{})), true)) || ...);
+    return rc;
+}
+
 // bytes of one stored element; 0 for an unknown dtype (every entry point checks dtype_valid first: a garbage dtype must not be
 // sized as a 2-byte type)
 static inline int elem_size(int dtype) { return dtype == YOLO_F32 ? 4 : (dtype == YOLO_BF16 || dtype == YOLO_F16 || dtype == YOLO_BF16X3 || dtype == YOLO_F16X3) ? 2 : 0; }

@@ -47,7 +47,7 @@ struct ConvArgs {
     long long r_bs, r_ps;   // residual strides (elements); differ from y's when y is a channel slice of a wider buffer
     FastDiv d_PW, d_H1, d_TWt, d_Ho, d_HoWo, d_tc, d_tps;   // divisors PW, H+1, TWt, Ho, Ho*Wo, tiles_c, tiles_per_strip
     // BatchNorm batch statistics folded into the epilogue (training step; conv_epilogue.h): per (pixel tile, pixel wave)
-    // partial column sums [rows][2][Cout_pad] fp32, summed in double by bn_stats_finish_kernel (train.hip)
+    // partial column sums [rows][2][Cout_pad] fp32, summed in double by bn_stats_finish_kernel (bn_train.hip)
     float* stats;           // nullptr: none
     int stats_mode;         // 1: sum(y), sum(y^2) of the output; 2: sum(da), sum(da * xhat) of the BatchNorm BEHIND the output
     const char* s_y;        // mode 2: that layer's raw convolution output (same shape as the output here), dense

@@ -1,5 +1,6 @@
 // HBM-bound plumbing kernels: layout conversion, BN folding, up-sample + concat.
 #include "common.h"
+#include "train_access.h"
 
 extern "C" int yolo_version(void) { return YOLO_ABI_VERSION; }
 
@@ -38,6 +39,8 @@ extern "C" int yolo_fold_bn(const float* gamma, const float* beta, const float* 
 // ---- NCHW f32 -> NHWC(Cpad) dtype ----------------------------------------------------------
 // One thread per pixel: reads are coalesced along W in every channel plane (NCHW), the write is
 // one contiguous Cpad-channel vector per pixel.
+// Split types: the Cpad channels of a pixel as a hi and a lo vector, round_up(Cpad, 32) elements apart (dense split storage); the
+// pad channels beyond Cpad of each plane are not written.
 template <typename T, int CPAD>
 __global__ void nchw_to_nhwc_kernel(const float* __restrict__ x, T* __restrict__ y, int C, long long HW,
                                     long long total) {
@@ -51,9 +54,16 @@ __global__ void nchw_to_nhwc_kernel(const float* __restrict__ x, T* __restrict__
         uint32_t w[CPAD / 2];
 #pragma unroll
         for (int c = 0; c < CPAD / 2; ++c) w[c] = Elem<T>::pack2(v[2 * c], v[2 * c + 1]);
-        uint4* dst = (uint4*)((uint16_t*)y + p * CPAD);
+        uint4* dst = (uint4*)((uint16_t*)y + p * dense_ps<T>(CPAD));
 #pragma unroll
         for (int q = 0; q < CPAD / 8; ++q) dst[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+        if constexpr (IsSplit<T>::value) {
+#pragma unroll
+            for (int c = 0; c < CPAD / 2; ++c) w[c] = split_lo_bf16x2(v[2 * c], v[2 * c + 1], w[c]);
+            dst += dense_lo<T>(CPAD) / 8;
+#pragma unroll
+            for (int q = 0; q < CPAD / 8; ++q) dst[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+        }
     } else {
         f32x4* dst = (f32x4*)((float*)y + p * CPAD);
 #pragma unroll
@@ -64,46 +74,18 @@ __global__ void nchw_to_nhwc_kernel(const float* __restrict__ x, T* __restrict__
     }
 }
 
-// split form (YOLO_BF16X3): the Cpad = 8 channels of a pixel as a hi and a lo octet, round_up(8, 32) = 32 elements apart (dense
-// split storage, pixel stride 64); the 24 pad channels of each plane are not written
-__global__ void nchw_to_nhwc_split_kernel(const float* __restrict__ x, uint16_t* __restrict__ y, int C, long long HW, long long total) {
-    const long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (p >= total) return;
-    const long long n = p / HW, hw = p - n * HW;
-    uint32_t h[4], l[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float a = (2 * q < C) ? x[(n * C + 2 * q) * HW + hw] : 0.f;
-        const float b = (2 * q + 1 < C) ? x[(n * C + 2 * q + 1) * HW + hw] : 0.f;
-        h[q] = pack_bf16x2(a, b);
-        l[q] = pack_bf16x2(a - bf16_bits_to_f32(h[q] & 0xffffu), b - bf16_bits_to_f32(h[q] >> 16));
-    }
-    uint4* dst = (uint4*)(y + p * 64);
-    dst[0] = make_uint4(h[0], h[1], h[2], h[3]);
-    dst[4] = make_uint4(l[0], l[1], l[2], l[3]);
-}
-
 extern "C" int yolo_nchw_to_nhwc(const float* x, void* y, int N, int C, int H, int W, int Cpad, int dtype,
                                  void* stream) {
     if (!x || !y || N <= 0 || C <= 0 || H <= 0 || W <= 0) return YOLO_EINVAL;
     if (Cpad != 8 || C > 8) return YOLO_EUNSUPPORTED;
     const long long HW = (long long)H * W, total = HW * N;
     const unsigned grid = (unsigned)((total + 255) / 256);
-    if (dtype == YOLO_BF16X3)
-        YOLO_LAUNCH(nchw_to_nhwc_split_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (uint16_t*)y, C, HW, total);
-    else if (dtype == YOLO_BF16)
-        YOLO_LAUNCH((nchw_to_nhwc_kernel<bf16_t, 8>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x,
-                           (bf16_t*)y, C, HW, total);
-    else if (dtype == YOLO_F16)
-        YOLO_LAUNCH((nchw_to_nhwc_kernel<f16_t, 8>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x,
-                           (f16_t*)y, C, HW, total);
-    else if (dtype == YOLO_F32)
-        YOLO_LAUNCH((nchw_to_nhwc_kernel<float, 8>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x,
-                           (float*)y, C, HW, total);
-    else
-        return YOLO_EINVAL;
-    YOLO_LAUNCH_CHECK();
-    return YOLO_OK;
+    return dispatch_dtype<float, bf16_t, f16_t, bf16x3_t>(dtype, [&](auto t) {
+        using T = decltype(t);
+        YOLO_LAUNCH((nchw_to_nhwc_kernel<T, 8>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (T*)y, C, HW, total);
+        YOLO_LAUNCH_CHECK();
+        return YOLO_OK;
+    });
 }
 
 // ---- (N,H,W,C) u8 -> (N,C,H,W) f32 / 255  (cv_img_2_ndarray, yolo_gluon.py:335-357) ----------
@@ -145,23 +127,19 @@ extern "C" int yolo_nhwc_to_nchw(const void* x, float* y, int N, int C, int H, i
     if (!x || !y || N <= 0 || C <= 0 || H <= 0 || W <= 0) return YOLO_EINVAL;
     const long long HW = (long long)H * W, total = HW * N * C;
     const unsigned grid = (unsigned)((total + 255) / 256);
-    if (dtype == YOLO_BF16)
-        YOLO_LAUNCH(nhwc_to_nchw_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_t*)x, y, C, HW, total);
-    else if (dtype == YOLO_F16)
-        YOLO_LAUNCH(nhwc_to_nchw_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                           (const f16_t*)x, y, C, HW, total);
-    else if (dtype == YOLO_F32)
-        YOLO_LAUNCH(nhwc_to_nchw_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                           (const float*)x, y, C, HW, total);
-    else
-        return YOLO_EINVAL;
-    YOLO_LAUNCH_CHECK();
-    return YOLO_OK;
+    return dispatch_dtype<float, bf16_t, f16_t>(dtype, [&](auto t) {
+        using T = decltype(t);
+        YOLO_LAUNCH(nhwc_to_nchw_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)x, y, C, HW, total);
+        YOLO_LAUNCH_CHECK();
+        return YOLO_OK;
+    });
 }
 
 // ---- 2x nearest up-sample + channel concat (car/utils.py:92-93) ----------------------------
 // 16-byte units; unit q of output pixel (n,y,x): q < U1 -> up[n, y/2, x/2], else route[n, y, x].
+// PLANES = 2: dense split up, route and y, whose units hold 8 channels: a pixel is its hi units, padded to a multiple of 4 (32
+// channels), then as many lo units, and both planes of a unit are copied as they are; the pad units of y are not written.
+template <int PLANES>
 __global__ void upsample_concat_kernel(const uint4* __restrict__ up, const uint4* __restrict__ route,
                                        uint4* __restrict__ y, int H, int W, int U1, int U2, long long total) {
     const long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
@@ -169,64 +147,42 @@ __global__ void upsample_concat_kernel(const uint4* __restrict__ up, const uint4
     const int U = U1 + U2;
     const long long pix = idx / U;
     const int q = (int)(idx - pix * U);
+    // lo offset and pixel stride of a tensor with u units per pixel and plane
+    auto lo_of = [](int u) { return PLANES == 2 ? round_up(u, 4) : 0; };
+    auto ps_of = [](int u) { return PLANES == 2 ? 2LL * round_up(u, 4) : u; };
+    uint4* o = y + (PLANES == 2 ? pix * ps_of(U) + q : idx);
+    auto copy = [&](const uint4* s, int lo) {
+#pragma unroll
+        for (int k = 0; k < PLANES; ++k) o[k * lo_of(U)] = s[k * lo];
+    };
     if (q >= U1) {
-        y[idx] = route[pix * U2 + (q - U1)];
+        copy(&route[pix * ps_of(U2) + (q - U1)], lo_of(U2));
     } else {
         const long long HW = (long long)H * W;
         const long long n = pix / HW;
         const int hw = (int)(pix - n * HW);
         const int yy = hw / W, xx = hw - yy * W;
         const long long sp = (n * (H / 2) + (yy >> 1)) * (W / 2) + (xx >> 1);
-        y[idx] = up[sp * U1 + q];
+        copy(&up[sp * ps_of(U1) + q], lo_of(U1));
     }
-}
-
-// split form: dense split up (C1), route (C2) and y (C1 + C2 channels); per output pixel and plane, 8-channel units of up then route
-// (C1 % 8 == 0 and C2 % 8 == 0); the pad channels of y are not written
-__global__ void upsample_concat_split_kernel(const uint16_t* __restrict__ up, const uint16_t* __restrict__ route,
-                                             uint16_t* __restrict__ y, int H, int W, int C1, int C2, long long total) {
-    const long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int U1 = C1 / 8, U = (C1 + C2) / 8;
-    const long long pix = idx / U;
-    const int q = (int)(idx - pix * U);
-    const long long ps1 = 2LL * round_up(C1, 32), ps2 = 2LL * round_up(C2, 32), psy = 2LL * round_up(C1 + C2, 32);
-    const uint16_t* s;
-    long long lo;
-    if (q >= U1) {
-        s = route + pix * ps2 + (q - U1) * 8;
-        lo = ps2 / 2;
-    } else {
-        const long long HW = (long long)H * W;
-        const long long n = pix / HW;
-        const int hw = (int)(pix - n * HW);
-        const int yy = hw / W, xx = hw - yy * W;
-        s = up + ((n * (H / 2) + (yy >> 1)) * (W / 2) + (xx >> 1)) * ps1 + q * 8;
-        lo = ps1 / 2;
-    }
-    uint16_t* o = y + pix * psy + q * 8;
-    *(uint4*)o = *(const uint4*)s;
-    *(uint4*)(o + psy / 2) = *(const uint4*)(s + lo);
 }
 
 extern "C" int yolo_upsample2x_concat(const void* up, const void* route, void* y, int N, int H, int W, int C1,
                                       int C2, int dtype, void* stream) {
     if (!up || !route || !y || N <= 0 || H <= 0 || W <= 0 || C1 <= 0 || C2 <= 0) return YOLO_EINVAL;
-    if (dtype == YOLO_BF16X3 && !(H & 1) && !(W & 1)) {
-        if ((C1 % 8) || (C2 % 8)) return YOLO_EUNSUPPORTED;
-        const long long total = (long long)N * H * W * ((C1 + C2) / 8);
-        YOLO_LAUNCH(upsample_concat_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                    (const uint16_t*)up, (const uint16_t*)route, (uint16_t*)y, H, W, C1, C2, total);
-        YOLO_LAUNCH_CHECK();
-        return YOLO_OK;
-    }
-    if ((H & 1) || (W & 1) || !dtype_plain(dtype)) return YOLO_EINVAL;
-    const int es = elem_size(dtype);
-    if ((C1 * es) % 16 || (C2 * es) % 16) return YOLO_EUNSUPPORTED;
-    const int U1 = C1 * es / 16, U2 = C2 * es / 16;
+    const bool split = dtype == YOLO_BF16X3;
+    if ((H & 1) || (W & 1) || !(split || dtype_plain(dtype))) return YOLO_EINVAL;
+    const int per = split ? 8 : 16 / elem_size(dtype);             // channels of a 16-byte unit
+    if ((C1 % per) || (C2 % per)) return YOLO_EUNSUPPORTED;
+    const int U1 = C1 / per, U2 = C2 / per;
     const long long total = (long long)N * H * W * (U1 + U2);
-    YOLO_LAUNCH(upsample_concat_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, (const uint4*)up, (const uint4*)route, (uint4*)y, H, W, U1, U2, total);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (split)
+        YOLO_LAUNCH(upsample_concat_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, (const uint4*)up, (const uint4*)route,
+                    (uint4*)y, H, W, U1, U2, total);
+    else
+        YOLO_LAUNCH(upsample_concat_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, (const uint4*)up, (const uint4*)route,
+                    (uint4*)y, H, W, U1, U2, total);
     YOLO_LAUNCH_CHECK();
     return YOLO_OK;
 }

@@ -4,7 +4,7 @@
 // MFMA 32x32x16 bf16 with K = output pixels; both operands are [pixel][channel] in HBM, so the fragments come from
 // the transposing LDS read ds_read_b64_tr_b16 (tools/probes/tr_b16_probe.hip).
 //
-// What the older kernels of train.hip leave on the table (wgrad_rows_kernel: ~600 TFLOP/s on the 26x26 / 13x13 maps,
+// What the older kernels of wgrad.hip leave on the table (wgrad_rows_kernel: ~600 TFLOP/s on the 26x26 / 13x13 maps,
 // the per-tap wgrad_bf16_kernel: less on the 52x52 ones): they stage through registers behind two __syncthreads per
 // chunk, and they read NINE shifted x fragments from LDS for every dy fragment (ten fragment reads per nine MFMAs;
 // ds_read_b64 needs ~4 waves per SIMD to reach its rate, these kernels hold two).  Here:
@@ -26,6 +26,7 @@
 // accumulators through LDS first: 256 contiguous bytes per atomic instruction, no workspace, no finishing pass).
 #include "common.h"
 #include "conv_args.h"
+#include "wgrad_walk.h"
 #include <type_traits>
 #include <stdlib.h>
 
@@ -557,7 +558,7 @@ int wgrad_gemm_dispatch(const void* dy, const void* x, float* dw, long long P, i
 }
 
 // variant: 0 = the default; 1 = one 16-column walker; 2 = four 4-column walkers; 3 = 2, with 8-wave blocks of two K-halves.  EUNSUPPORTED when the
-// shape is outside the kernel's domain (the caller falls back on the kernels of train.hip).
+// shape is outside the kernel's domain (the caller falls back on the kernels of wgrad.hip).
 int wgrad_walk_dispatch(const void* dy, const void* x, float* dwt, int N, int H, int W, int Cin, int Cout, long long ps,
                         int variant, hipStream_t st) {
     if ((Cin % 64) || (Cout % 64) || (ps % 8) || W < 4 || H < 2) return YOLO_EUNSUPPORTED;

@@ -2,7 +2,7 @@
 BatchNorm, target assignment (_find_best/_loss_mask), the five losses (_get_loss), backward of
 sum(losses), gradient all-reduce over ranks and the MXNet Adam update of trainer.step(batch_size).
 
-fp32 parity path: every op is a HIP kernel from libyolo_amd.so (train.hip, loss.hip and the forward conv
+fp32 parity path: every op is a HIP kernel from libyolo_amd.so (bn_train.hip, wgrad.hip, train_ops.hip, loss.hip and the forward conv
 kernels re-used for the data gradient on flipped weights); torch owns memory, the stream and the
 process group only.  dtype 'bf16x3' (the split-bf16 path, include/yolo_amd.h YOLO_BF16X3) runs the same graph on (hi, lo) pairs:
 the fp32 arithmetic of the reference to ~16 significant bits at the bf16 MFMA rate.  One process per GPU; BN statistics stay local to the GPU (no SyncBN,
