@@ -292,6 +292,33 @@ int yolo_decode_nms(const float* out, float* rows, float* scores, int B, int C, 
                     float valid_thresh, float iou_thresh, int topk, int post_nms, int* kept, float* kept_scores,
                     int* kept_count, void* select_workspace, void* stream);
 
+/* ---- evaluation (detection quality on the device) -------------------------------------------- */
+
+/* Matching of ranked detections to ground truth, PASCAL-VOC devkit semantics (no counterpart in the reference, whose only
+ * quality figures are the top-1 ones below; scores what the per-class NMS of SURVEY App. A.8 keeps).  rows (B, nbox, C) decoded
+ * rows, kept (B, post_nms) / kept_count (B) as yolo_nms_from_scores / yolo_decode_nms return them (candidate id = box *
+ * cand_per_box + class); labels (B, nobj, label_cols >= 5) float32 in the training layout [cls, y, x, h, w, ...] (car/YOLO.py:525),
+ * cls < 0 = no object.  Per detection, in kept (= score) order: the valid ground truth (of the detection's class when
+ * class_aware) with the largest IoU, lowest index among equals; a true positive iff that IoU > iou_thresh and no earlier
+ * detection chose the same ground truth above the threshold (a later one is a false positive: no second choice).
+ * Outputs, one slot per (image, kept position): det_class, det_tp (1 / 0), det_gt (-1: none), det_iou; slots at or beyond
+ * kept_count, or holding an id outside [0, nbox * cand_per_box), are pads: class -1, tp -1, gt -1, iou 0.  gt_class (B, nobj):
+ * int(cls), 0 for every valid label when not class_aware, -1 for no object.  One block per image, no global atomics:
+ * bitwise reproducible.  nobj <= 512 and post_nms <= 1024 (YOLO_EUNSUPPORTED beyond). */
+int yolo_eval_match_supported(int nobj, int post_nms);
+int yolo_eval_match(const float* rows, const int* kept, const int* kept_count, const float* labels, int B, int nbox, int C,
+                    int cand_per_box, int post_nms, int nobj, int label_cols, int class_aware, float iou_thresh,
+                    int* det_class, int* det_tp, int* det_gt, float* det_iou, int* gt_class, void* stream);
+
+/* The per-image arithmetic of _valid_iou (car/YOLO.py:501-534) plus the azimuth of RadarProb.cls2ang (yolo_cv.py:85-95):
+ * pred (B, C) = yolo_predict_top1's rows [score, y, x, h, w, rot, cls...]; labels (B, nobj, label_cols) as above, only object 0
+ * of an image is read (car/YOLO.py:525); class_dirs (C - 6, 2) float32 [cos, sin] of the class azimuths.  out (B, 4), 16-byte
+ * aligned: [iou, azimuth (rad), radius, valid] -- iou = get_iou(mode 2) of the box rebuilt as car/YOLO.py:518-521 does,
+ * azimuth = atan2(sum sin p, sum cos p) with p = softmax(cls logits), radius = score * |mean direction|, valid = cls >= 0
+ * (an image without an object is marked invalid; the reference scores it against a box of -1s). */
+int yolo_eval_top1(const float* pred, const float* labels, const float* class_dirs, float* out, int B, int C, int nobj,
+                   int label_cols, void* stream);
+
 /* ---- training step (fp32 parity path) ------------------------------------------------------- */
 
 /* Packed weight image of the data-gradient convolution of a forward conv (Cout_f, Cin_f, k): dx =

@@ -11,4 +11,7 @@ def __getattr__(name):
     if name in ('Detector', 'get_iou', 'cv_img_2_ndarray', 'make_grid', 'predict_LP', 'predict_LP_batch', 'default_ltrb'):
         from . import detect
         return getattr(detect, name)
+    if name == 'Evaluator':
+        from . import evaluate
+        return evaluate.Evaluator
     raise AttributeError(name)

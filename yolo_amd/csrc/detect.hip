@@ -2,6 +2,7 @@
 // Compiled with -ffp-contract=off so fp32 arithmetic follows the reference's op-by-op NDArray
 // evaluation (no fused multiply-add), which is what makes index parity exact.
 #include "common.h"
+#include "iou.h"
 #include <atomic>
 #include <float.h>
 #include <string.h>
@@ -170,25 +171,14 @@ extern "C" int yolo_predict_top1(const float* out, float* pred, int* best_idx, i
     return YOLO_OK;
 }
 
-// ---- get_iou(predict, target, mode), yolo_gluon.py:127-168 ------------------------------------
-// MODE 2: target = [c, y, x, h, w] (the hot path: car/YOLO.py:403,525).  MODE 1 (the reference's default): target =
-// [c, l, t, r, b] -- including its target_area = target[3] * target[4] (yolo_gluon.py:166), i.e. r2 * b2 in this mode.
+// ---- get_iou(predict, target, mode), yolo_gluon.py:127-168 (arithmetic: get_iou_ref, iou.h) --------
 template <int MODE>
 __global__ void iou_kernel(const float* __restrict__ boxes, const float* __restrict__ target,
                            float* __restrict__ iou, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float t1 = target[1], t2_ = target[2], t3 = target[3], t4 = target[4];
-    float l2, t2, r2, b2;
-    if (MODE == 1) { l2 = t1; t2 = t2_; r2 = t3; b2 = t4; }
-    else { l2 = t2_ - t4 / 2.f; t2 = t1 - t3 / 2.f; r2 = t2_ + t4 / 2.f; b2 = t1 + t3 / 2.f; }
     const float4 p = ((const float4*)boxes)[i];     // l,t,r,b
-    const float iw = fmaxf(fminf(r2, p.z) - fmaxf(l2, p.x), 0.f);
-    const float ih = fmaxf(fminf(b2, p.w) - fmaxf(t2, p.y), 0.f);
-    const float inter = iw * ih;
-    const float pa = (p.z - p.x) * (p.w - p.y);
-    const float ta = t3 * t4;
-    iou[i] = inter / (pa + ta - inter);
+    iou[i] = get_iou_ref<MODE>(p, target[1], target[2], target[3], target[4]);
 }
 
 extern "C" int yolo_iou_ltrb_vs_yxhw(const float* boxes, const float* target, float* iou, int n, void* stream) {
@@ -626,14 +616,6 @@ __global__ __launch_bounds__(256) void nms_collect_kernel(const float* __restric
     }
 }
 
-
-__device__ __forceinline__ float box_iou(const float4 a, const float4 b) {
-    const float iw = fmaxf(0.f, fminf(a.z, b.z) - fmaxf(a.x, b.x));
-    const float ih = fmaxf(0.f, fminf(a.w, b.w) - fmaxf(a.y, b.y));
-    const float inter = iw * ih;
-    const float ua = (a.z - a.x) * (a.w - a.y) + (b.z - b.x) * (b.w - b.y) - inter;
-    return ua > 0.f ? inter / ua : 0.f;
-}
 
 __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* __restrict__ rows,
                                                           const float* __restrict__ scores, int nbox, int C, int cpb,

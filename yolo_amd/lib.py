@@ -89,6 +89,9 @@ SIGNATURES = {
     'yolo_nms_from_scores': (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'yolo_decode_nms': (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(GridDesc), _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'yolo_nms': (_i, [_vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'yolo_eval_match_supported': (_i, [_i, _i]),
+    'yolo_eval_match': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'yolo_eval_top1': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'yolo_pack_conv_weights_dgrad': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'yolo_pack_conv_weights_dgrad_s2': (_i, [_vp, _vp, _i, _i, _i, _vp]),
     'yolo_conv_dgrad_s2': (_i, [C.POINTER(ConvDesc), _vp]),
