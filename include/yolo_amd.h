@@ -85,6 +85,25 @@ int yolo_nchw_to_nhwc(const float* x, void* y, int N, int C, int H, int W, int C
 /* (N,H,W,C) uint8 -> (N,C,H,W) float32 / 255: cv_img_2_ndarray, yolo_gluon.py:335-357. */
 int yolo_image_u8_to_nchw(const unsigned char* img, float* y, int N, int H, int W, int C,
                           void* stream);
+/* Frame intake: inverse-mapped bilinear sampling of uint8 frames into the net's input.  Clip + flip + resize
+ * (yolo_cv.py:285-318 cv2_flip_and_clip_frame, cv2.resize, yolo_gluon.py:335-357 cv_img_2_ndarray) are one affine M; the plate
+ * rectification of ProjectRectangle6D.add_edges (licence_plate_render/__init__.py:379-402) is one homography.
+ * frames (N,Hs,Ws,C) u8 dense, y (N,C,Ho,Wo) f32 dense, M (N,9) f32 ON THE DEVICE, row-major 3x3 mapping an OUTPUT pixel
+ * (column j, row i) to SOURCE pixel coordinates (integer = pixel centre, cv2's WARP_INVERSE_MAP convention);
+ * border 0 = taps outside roi read 0 (cv2.warpPerspective's default), 1 = tap indices clamped into roi (cv2.resize on a crop);
+ * roi = {x0, y0, x1, y1} inclusive, host ints, shared by the batch; gain: C floats on the device or NULL (= 1).
+ * The arithmetic, every operation in fp32, in this order, nothing fused (this is the definition; tests/intake_ref.py restates it):
+ *   u = (m0*j + m1*i) + m2;  v = (m3*j + m4*i) + m5;  w = (m6*j + m7*i) + m8;     sx = u / w;  sy = v / w
+ *   x0 = floor(sx), fx = sx - x0;  y0 = floor(sy), fy = sy - y0
+ *   taps a = (y0, x0), b = (y0, x0+1), c = (y0+1, x0), d = (y0+1, x0+1), each converted to float
+ *   top = a + fx*(b - a);  bot = c + fx*(d - c);  val = top + fy*(bot - top);     y = (val / 255.f) * gain[ch]
+ * Channel order is untouched.  x0 / y0 are limited to +-2^30 before they become integers; a coordinate that is not a number
+ * (w = 0) indexes outside and gives NaN through fx / fy.  No load leaves the roi whatever M holds.
+ * YOLO_EINVAL: a NULL frames / y / M, a non-positive size, a roi that is empty or not inside the frame.  YOLO_EUNSUPPORTED:
+ * C > 4, a border not in {0, 1} (and Ho * ceil(Wo / 4) or Ws * C beyond 2^31).  16-byte plane stores when Wo % 4 == 0 and y is
+ * 16-byte aligned, scalar stores otherwise. */
+int yolo_warp_u8_to_nchw(const unsigned char* frames, float* y, const float* M, const float* gain, int N, int Hs, int Ws, int C,
+                         int Ho, int Wo, int border, int roi_x0, int roi_y0, int roi_x1, int roi_y1, void* stream);
 /* NHWC dtype -> NCHW float32 (debug / parity taps). */
 int yolo_nhwc_to_nchw(const void* x, float* y, int N, int C, int H, int W, int dtype, void* stream);
 

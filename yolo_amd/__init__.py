@@ -14,4 +14,7 @@ def __getattr__(name):
     if name == 'Evaluator':
         from . import evaluate
         return evaluate.Evaluator
+    if name in ('FrameIntake', 'intake_matrix', 'warp_u8', 'rectify_plates'):
+        from . import intake
+        return getattr(intake, name)
     raise AttributeError(name)

@@ -65,6 +65,7 @@ SIGNATURES = {
     'yolo_nchw_to_nhwc': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'yolo_image_u8_to_nchw': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'yolo_nhwc_to_nchw': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'yolo_warp_u8_to_nchw': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'yolo_conv_fwd': (_i, [C.POINTER(ConvDesc), _vp]),
     'yolo_conv_kernel_name': (_i, [C.POINTER(ConvDesc), C.c_char_p, _i]),
     'yolo_conv_stats_rows': (_i, [C.POINTER(ConvDesc)]),
