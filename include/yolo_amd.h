@@ -230,6 +230,42 @@ int yolo_composite(const float* bg, const float* fg, const float* mask, float* o
  * onto images that are ALREADY 0..1: out = clip(bg * (1 - mask) + fg * mask, 0, 1). */
 int yolo_composite_unit(const float* bg, const float* fg, const float* mask, float* out, long long n, void* stream);
 
+/* RenderCar.render (car/render_car.py:52-138) with the PIXELS made on the device: the host decides (sprite, scale, angle, blur,
+ * offset, colour: yolo_amd/render.py draw_params) and hands over one row of YOLO_RENDER_ROW_WORDS 32-bit words per image:
+ *   0 has-sprite (int)     1 h  2 w: the mip level's size (int)      3..6 window l, t, r, b (int; r, b exclusive)     7 unused
+ *   8,9 the level's byte offset in the atlas (one 64-bit int)        10..15 a0..a5 (float)     16 w0  17 w1 (float)
+ *   18..26 A  27..35 D (3x3 row-major, float)   36..38 e (float)     39 unused
+ * atlas: uint8 RGBA levels packed as (h, w, 4), atlas_bytes in all, 4-byte aligned; rows ON THE DEVICE, 8-byte aligned;
+ * bg (N,3,H,W) f32 0..255, out (N,3,H,W) f32 0..1, dense.  The arithmetic, every operation in fp32, in this order, nothing fused
+ * (this is the definition; tests/render_ref.py restates it):
+ *  the sample S(x, y) at output position (column x, row y), four channels RGBA interpolated independently:
+ *   sx = (a0*x + a1*y) + a2;  sy = (a3*x + a4*y) + a5;   x0 = floor(sx), fx = sx - x0;  y0 = floor(sy), fy = sy - y0
+ *   taps a = (y0, x0), b = (y0, x0+1), c = (y0+1, x0), d = (y0+1, x0+1): a tap inside the level reads its byte as a float, one
+ *   outside reads 0;   top = a + fx*(b - a);  bot = c + fx*(d - c);  S = top + fy*(bot - top)
+ *  the value at output pixel (j, i):  w1 == 0:  P = S(j, i);   otherwise, with R(dy) = (w1*S(j-1, i+dy) + w0*S(j, i+dy)) + w1*S(j+1, i+dy),
+ *   P = (w1*R(-1) + w0*R(0)) + w1*R(1)       (a 3x3 separable blur; NOT PIL's box-blur GaussianBlur)
+ *  yolo_render_stats: per image and channel c of R, G, B the sum of P_c over the window's pixels, each converted to double and added
+ *   in double, as RENDER_STAT_BLOCKS = 16 partial sums (workspace: yolo_render_workspace_bytes(N, H, W) bytes, 8-byte aligned,
+ *   caller-owned); no atomics, so the sums do not depend on scheduling.
+ *  yolo_render_cars: sum_c = the image's partials added in index order (double);  mu_c = (float)(sum_c / (double)(H*W));
+ *   k_c = ((D[c][0]*mu_0 + D[c][1]*mu_1) + D[c][2]*mu_2) + e_c;      per pixel of the window:
+ *   fg_c = (((A[c][0]*P_0 + A[c][1]*P_1) + A[c][2]*P_2) + k_c) / 255.f;   mask = P_3 / 255.f
+ *   out_c = min(max((bg_c / 255.f) * (1.f - mask) + fg_c * mask, 0), 1)          (yolo_composite's operation order)
+ *  A pixel outside the window, and every pixel of an image without a sprite: out_c = min(max(bg_c / 255.f, 0), 1), the atlas is
+ *  not touched.  x0 / y0 are limited to +-2^30 before they become integers.  No load leaves the atlas whatever a row holds: a row
+ *  whose level (offset not a multiple of 4, or offset + 4 h w beyond atlas_bytes, or h, w <= 0) does not lie inside the atlas is
+ *  "no sprite", the window is clipped to the canvas, tap addresses are clamped into the level.
+ * YOLO_EINVAL: a NULL pointer, a non-positive N, H, W or atlas_bytes, a misaligned atlas / rows / workspace.  YOLO_EUNSUPPORTED:
+ * H * ceil(W / 4) beyond 2^31.  yolo_render_workspace_bytes returns YOLO_EINVAL for a non-positive size.
+ * 16-byte bg loads and plane stores when W % 4 == 0 and bg, out are 16-byte aligned, scalar ones otherwise.
+ * yolo_render_cars must follow yolo_render_stats on the same rows, in stream order. */
+#define YOLO_RENDER_ROW_WORDS 40
+long long yolo_render_workspace_bytes(int N, int H, int W);
+int yolo_render_stats(const unsigned char* atlas, long long atlas_bytes, const void* rows, void* workspace, int N, int H, int W,
+                      void* stream);
+int yolo_render_cars(const float* bg, const unsigned char* atlas, long long atlas_bytes, const void* rows, const void* workspace,
+                     float* out, int N, int H, int W, void* stream);
+
 /* 2x nearest up-sample of `up` (N,H/2,W/2,C1) + channel concat with `route` (N,H,W,C2) ->
  * (N,H,W,C1+C2), up-sampled channels first: gluoncv _upsample + F.concat, car/utils.py:92-93. */
 int yolo_upsample2x_concat(const void* up, const void* route, void* y, int N, int H, int W,

@@ -6,6 +6,9 @@ are training data that is not part of the reference repository: RenderCar takes 
     label row = [cls, y, x, h, w, r, class distribution...]   (render_car.py:66-67,124-133)
     cls / distribution = get_label_dist(ele, azi)             (render_car.py:410-438)
     image = clip(bg / 255 * (1 - mask) + fg * mask, 0, 1)     (render_car.py:135-137)   -> yolo_composite (HIP)
+
+RenderCar.render_device makes the same batch with the PIXELS drawn on the device too (csrc/render.hip): the host only makes the
+draws (draw_params: one row of scalars per image), a resident uint8 RGBA SpriteAtlas holds the sprites and their mip levels.
 """
 import math
 import os
@@ -111,6 +114,156 @@ class ColorAugmenter(object):
         src = src @ np.dot(np.dot(self.ITYIQ, bt), self.TYIQ).T.astype(np.float32)
         a = np.random.normal(0, self.pca, size=(3,))              # LightingAug
         return (src + np.dot(self.EIGVEC * a, self.EIGVAL).astype(np.float32)).astype(np.float32)
+
+    def affine(self):
+        """The whole chain as ONE map  out = A x + D mean(x) + e  (x: a pixel, mean(x): the per-channel mean of the image the
+        chain is given), float64 (A (3,3), D (3,3), e (3,)).  Every stage is affine in the pixel; only contrast looks at the
+        image, through its mean.  Makes __call__'s draws, in __call__'s order, from the same `random` / `np.random` streams."""
+        coef = self.COEF.reshape(3).astype(np.float64)
+        gray = np.outer(np.ones(3), coef)                         # every channel <- the luma of the pixel
+        st = {'A': np.eye(3), 'D': np.zeros((3, 3)), 'e': np.zeros(3)}
+
+        def left(M):
+            st['A'], st['D'], st['e'] = M @ st['A'], M @ st['D'], M @ st['e']
+
+        def brightness():
+            left(np.eye(3) * float(np.float32(1.0 + random.uniform(-self.b, self.b))))
+
+        def contrast():
+            alpha = 1.0 + random.uniform(-self.c, self.c)
+            # gray = (1 - alpha) * luma of the MEAN of what this stage is given = coef . ((A + D) mean(x) + e)
+            add_d, add_e = (1.0 - alpha) * gray @ (st['A'] + st['D']), (1.0 - alpha) * gray @ st['e']
+            left(np.eye(3) * float(np.float32(alpha)))
+            st['D'], st['e'] = st['D'] + add_d, st['e'] + add_e
+
+        def saturation():
+            alpha = 1.0 + random.uniform(-self.s, self.s)
+            left(np.eye(3) * float(np.float32(alpha)) + float(np.float32(1.0 - alpha)) * gray)
+
+        ts = [brightness, contrast, saturation]
+        random.shuffle(ts)
+        for t in ts:
+            t()
+        alpha = random.uniform(-self.h, self.h)
+        u, w = math.cos(alpha * math.pi), math.sin(alpha * math.pi)
+        bt = np.array([[1.0, 0.0, 0.0], [0.0, u, -w], [0.0, w, u]])
+        left(np.dot(np.dot(self.ITYIQ, bt), self.TYIQ))
+        a = np.random.normal(0, self.pca, size=(3,))
+        st['e'] = st['e'] + np.dot(self.EIGVEC * a, self.EIGVAL)
+        return st['A'], st['D'], st['e']
+
+
+# ---- the device renderer's host side: sprite atlas, analytic boxes, parameter rows (csrc/render.hip) -----------------------
+# render_host draws every image with PIL; render_device makes the same DECISIONS on the host (which sprite, scale, angle, blur,
+# offset, colour) as a row of scalars per image and leaves the pixels to yolo_render_stats / yolo_render_cars.  One row is
+# ROW_WORDS 32-bit words (include/yolo_amd.h, yolo_render_cars):
+#   0 has-sprite   1 h   2 w (of the mip level)   3..6 window l, t, r, b (r, b exclusive)   8,9 the level's byte offset (int64)
+#   10..15 the inverse affine a0..a5   16 w0   17 w1   18..26 A   27..35 D   36..38 e        (7, 39: padding)
+ROW_WORDS = 40
+MIP_MIN_SIDE = 8
+BLUR_MIN_SIGMA = 0.05
+
+
+def convex_hull(pts):
+    """Andrew's monotone chain on an (n,2) array -> the hull's vertices (m,2) float64."""
+    pts = sorted(set(map(tuple, np.asarray(pts, np.float64).tolist())))
+    if len(pts) <= 2:
+        return np.asarray(pts, np.float64).reshape(-1, 2)
+
+    def half(seq):
+        out = []
+        for p in seq:
+            while len(out) >= 2 and ((out[-1][0] - out[-2][0]) * (p[1] - out[-2][1]) - (out[-1][1] - out[-2][1]) * (p[0] - out[-2][0])) <= 0:
+                out.pop()
+            out.append(p)
+        return out[:-1]
+    return np.asarray(half(pts) + half(pts[::-1]), np.float64)
+
+
+def pixel_hull(rgba):
+    """Convex hull of the CORNER points of the pixels of an (h,w,4) uint8 image that are non-zero in any band (the pixel set
+    PIL's getbbox(alpha_only=False) looks at), in continuous coordinates: pixel (row i, column j) is [j, j+1] x [i, i+1].
+    A sprite with no such pixel gets its whole rectangle (as _render_png does)."""
+    h, w = rgba.shape[:2]
+    on = (rgba != 0).any(axis=2)
+    rows = np.nonzero(on.any(axis=1))[0]
+    if len(rows) == 0:
+        return np.float64([[0, 0], [w, 0], [w, h], [0, h]])
+    first = on.argmax(axis=1)[rows]
+    last = w - on[:, ::-1].argmax(axis=1)[rows]                   # exclusive
+    pts = [(x, y) for xs in (first, last) for ys in (rows, rows + 1) for x, y in zip(xs.tolist(), ys.tolist())]
+    return convex_hull(pts)
+
+
+def mip_chain(rgba):
+    """[level 0, level 1, ...]: each level the 2x2 average (rounded to nearest) of the one before, an odd last row / column
+    dropped, down to the last level whose shorter side is still >= MIP_MIN_SIDE."""
+    levels = [np.ascontiguousarray(rgba, np.uint8)]
+    while min(levels[-1].shape[:2]) // 2 >= MIP_MIN_SIDE:
+        a = levels[-1]
+        h, w = a.shape[0] // 2 * 2, a.shape[1] // 2 * 2
+        a = a[:h, :w].astype(np.uint16)
+        levels.append(((a[0::2, 0::2] + a[0::2, 1::2] + a[1::2, 0::2] + a[1::2, 1::2] + 2) >> 2).astype(np.uint8))
+    return levels
+
+
+class SpriteAtlas(object):
+    """Every sprite as uint8 RGBA with its mip chain, packed densely ((h, w, 4) after (h, w, 4)) into ONE byte buffer
+    (`data`) that is uploaded once; `table[s]` lists (byte offset, h, w) per level of sprite s, `hull[s]` is pixel_hull of
+    its level 0 and `size[s]` its (h, w)."""
+
+    def __init__(self, sprites):
+        self.table, self.hull, self.size = [], [], []
+        chunks, off = [], 0
+        for rgba in sprites:
+            rgba = np.asarray(rgba, np.uint8)
+            if rgba.ndim != 3 or rgba.shape[2] != 4:
+                raise ValueError('sprites should be (h, w, 4) uint8 RGBA')
+            rows = []
+            for lv in mip_chain(rgba):
+                rows.append((off, lv.shape[0], lv.shape[1]))
+                chunks.append(lv.reshape(-1))
+                off += lv.size
+            self.table.append(rows)
+            self.hull.append(pixel_hull(rgba))
+            self.size.append((rgba.shape[0], rgba.shape[1]))
+        self.data = np.concatenate(chunks) if chunks else np.zeros(0, np.uint8)
+
+    def pick_level(self, s, scale):
+        """-> (level, residual scale = scale * 2**level): the level at which the residual lies in (0.5, 1], so that a plain
+        bilinear tap does not skip source pixels; the coarsest level the sprite has when that one does not exist (the
+        residual is then <= 0.5), level 0 for a magnification."""
+        level = 0
+        while scale * 2 ** level <= 0.5 and level + 1 < len(self.table[s]):
+            level += 1
+        return level, scale * 2 ** level
+
+
+def pil_rotate_matrix(w, h, deg):
+    """PIL's Image.rotate(deg, expand=1) as numbers: -> (nw, nh, M (3,3) float64) with M mapping a point of the rotated
+    (nw, nh) image to the point of the (w, h) image it shows, both in continuous coordinates (pixel k spans [k, k+1])."""
+    ang = -math.radians(deg % 360.0)
+    m = [round(math.cos(ang), 15), round(math.sin(ang), 15), 0.0, round(-math.sin(ang), 15), round(math.cos(ang), 15), 0.0]
+
+    def tf(x, y):
+        return m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5]
+    m[2], m[5] = tf(-w / 2., -h / 2.)
+    m[2] += w / 2.
+    m[5] += h / 2.
+    pts = [tf(x, y) for x, y in ((0, 0), (w, 0), (w, h), (0, h))]
+    nw = math.ceil(max(p[0] for p in pts)) - math.floor(min(p[0] for p in pts))
+    nh = math.ceil(max(p[1] for p in pts)) - math.floor(min(p[1] for p in pts))
+    m[2], m[5] = tf(-(nw - w) / 2.0, -(nh - h) / 2.0)
+    return nw, nh, np.array([m[:3], m[3:], [0.0, 0.0, 1.0]])
+
+
+def blur_weights(sigma):
+    """The 3-tap weights (w0 centre, w1 either side) of the device renderer's blur: w1 / w0 = exp(-1 / (2 sigma^2)),
+    normalised to w0 + 2 w1 = 1; no blur below BLUR_MIN_SIGMA.  (A definition of its own, not PIL's box-blur GaussianBlur.)"""
+    if sigma < BLUR_MIN_SIGMA:
+        return 1.0, 0.0
+    g = math.exp(-1.0 / (2.0 * sigma * sigma))
+    return 1.0 / (1.0 + 2.0 * g), g / (1.0 + 2.0 * g)
 
 
 def pascal3d_view(mat):
@@ -269,6 +422,190 @@ class RenderCar(object):
         dev = bg.device
         img = composite(bg, torch.from_numpy(fg).to(dev), torch.from_numpy(mask).to(dev))
         return img, torch.from_numpy(labels).to(dev)
+
+    # ---- the same batch drawn on the device (csrc/render.hip): decisions here, pixels there ----------------------------
+    def atlas(self):
+        """The SpriteAtlas of this object's sprites, built on first use: the PNG set (opened once, here) and the PASCAL3D+
+        crops; `_sprite_of[(kind, mode)][n]` is the atlas index of the n-th sprite of that list, `_png_view` its class and
+        class distribution (from the file name, as _render_png reads them on every draw)."""
+        if getattr(self, '_atlas', None) is None:
+            from PIL import Image
+            sprites, self._sprite_of, self._png_view = [], {}, {}
+            for mode, paths in self.rawcar_dataset.items():
+                self._sprite_of[('png', mode)] = list(range(len(sprites), len(sprites) + len(paths)))
+                self._png_view[mode] = []
+                for path in paths:
+                    img = path.split('/')[-1]
+                    ele = float(img.split('ele')[1].split('.')[0]) * math.pi / 18000.
+                    azi = float(img.split('azi')[1].split('_')[0]) * math.pi / 18000.
+                    self._png_view[mode].append(get_label_dist(ele, azi, self.classes))
+                    sprites.append(np.asarray(Image.open(path).convert('RGBA')))
+            for mode, data in self.pascal_dataset.items():
+                self._sprite_of[('pascal', mode)] = list(range(len(sprites), len(sprites) + len(data)))
+                sprites.extend(np.asarray(d[0]) for d in data)
+            self._atlas = SpriteAtlas(sprites)
+        return self._atlas
+
+    def _draw_png(self, mode, r1):
+        """_render_png's draws and its label box WITHOUT the pixels: the box is the bound of the sprite's pixel hull under
+        PIL's resize (to the integer size PIL resizes to) and rotate(expand=1) geometry.
+        -> (sprite, scale, map from the rotated image to level 0 (3,3), l, t, r, b, r, class, distribution, sigma); scale is
+        the SMALLER of the two axes' real scales (integer resized size over sprite size: the r1 aspect factor and int() move
+        them off the drawn number), which is what the mip level is picked from."""
+        atlas = self.atlas()
+        n = np.random.randint(len(self.rawcar_dataset[mode]))
+        s = self._sprite_of[('png', mode)][n]
+        img_cls, dist = self._png_view[mode][n]
+        h0, w0 = atlas.size[s]
+        resize = np.random.uniform(low=PNG_MIN_SCALE, high=PNG_MAX_SCALE)
+        rw, rh = int(resize * w0), int(resize * h0 * r1)
+        deg, r = 0.0, 0
+        if self.R != 0:
+            deg = np.random.uniform(low=-self.R, high=self.R)
+            r = float(deg * np.pi) / 180
+        sigma = np.random.rand() * self.G if self.G != 0 else 0.0
+        if rw <= 0 or rh <= 0:
+            raise ValueError('a %d x %d sprite at scale %g has no pixels' % (w0, h0, resize))
+        _, _, rot = pil_rotate_matrix(rw, rh, deg)
+        to_sprite = np.diag([w0 / float(rw), h0 / float(rh), 1.0]) @ rot
+        fwd = np.linalg.inv(to_sprite)
+        hull = atlas.hull[s]
+        px, py = fwd[0, 0] * hull[:, 0] + fwd[0, 1] * hull[:, 1] + fwd[0, 2], fwd[1, 0] * hull[:, 0] + fwd[1, 1] * hull[:, 1] + fwd[1, 2]
+        return s, min(rw / float(w0), rh / float(h0)), to_sprite, px.min(), py.min(), px.max(), py.max(), r, img_cls, dist, sigma
+
+    def _draw_pascal(self, mode, r1):
+        """_render_pascal's draws and its label box (the annotated box through the same arithmetic) without the pixels."""
+        atlas = self.atlas()
+        data = self.pascal_dataset[mode]
+        n = np.random.randint(len(data))
+        _, box, img_cls, dist = data[n]
+        s = self._sprite_of[('pascal', mode)][n]
+        h0, w0 = atlas.size[s]
+        box = np.asarray(box, np.float64)
+        span_w, span_h = box[2] - box[0], (box[3] - box[1]) * r1
+        hi = min(PASCAL_MAX_SCALE * self.w / span_w, PASCAL_MAX_SCALE * self.h / span_h)
+        lo = max(PASCAL_MIN_SCALE * self.w / span_w, PASCAL_MIN_SCALE * self.h / span_h)
+        scale = np.random.uniform(low=lo, high=hi)
+        new_w, new_h = scale * w0, scale * h0 * r1
+        rw, rh = int(new_w), int(new_h)
+        deg = np.random.uniform(low=-0.0, high=0.0)
+        r = float(deg * np.pi) / 180
+        sigma = np.random.rand() * self.G if self.G != 0 else 0.0
+        if rw <= 0 or rh <= 0:
+            raise ValueError('a %d x %d crop at scale %g has no pixels' % (w0, h0, scale))
+        _, _, rot = pil_rotate_matrix(rw, rh, deg)
+        to_sprite = np.diag([w0 / float(rw), h0 / float(rh), 1.0]) @ rot
+        cx = box[[0, 2]] * scale - 0.5 * new_w
+        cy = box[[1, 3]] * scale * r1 - 0.5 * new_h
+        gx, gy = np.meshgrid(cx, cy, indexing='ij')
+        rx, ry = gx * math.cos(r) - gy * math.sin(r), gy * math.cos(r) + gx * math.sin(r)
+        half_w = 0.5 * (abs(new_h * math.sin(r)) + abs(new_w * math.cos(r)))
+        half_h = 0.5 * (abs(new_h * math.cos(r)) + abs(new_w * math.sin(r)))
+        return (s, min(rw / float(w0), rh / float(h0)), to_sprite, rx.min() + half_w, ry.min() + half_h, rx.max() + half_w,
+                ry.max() + half_h, r, img_cls, dist, sigma)
+
+    def param_row(self, s, scale, to_sprite, paste_x, paste_y, sigma, color=None):
+        """One parameter row (ROW_WORDS int32 words, floats stored by bit pattern) for sprite s of the atlas drawn at
+        `scale` (the smaller axis scale: the other axis' residual can then pass 1 by the aspect factor, a slight magnification) with `to_sprite` (3,3) mapping the resized + rotated image to level 0 (continuous coordinates), pasted at the
+        integer offset (paste_x, paste_y); color = (A, D, e) or None for the identity.  The inverse affine takes an output
+        pixel INDEX (column j, row i) to a level pixel INDEX: half-pixel centres on both sides, composed in float64."""
+        atlas = self.atlas()
+        level, _ = atlas.pick_level(s, scale)
+        off, lh, lw = atlas.table[s][level]
+        paste = np.array([[1.0, 0.0, -float(paste_x)], [0.0, 1.0, -float(paste_y)], [0.0, 0.0, 1.0]])
+        cont = np.diag([0.5 ** level, 0.5 ** level, 1.0]) @ to_sprite @ paste          # canvas -> level, continuous
+        half = np.array([[1.0, 0.0, 0.5], [0.0, 1.0, 0.5], [0.0, 0.0, 1.0]])
+        M = np.linalg.inv(half) @ cont @ half
+        # the window: a sample is non-zero only where its level coordinate lies within half a pixel of the level's rectangle
+        fwd = np.linalg.inv(cont)
+        cx, cy = np.float64([-0.5, lw + 0.5, lw + 0.5, -0.5]), np.float64([-0.5, -0.5, lh + 0.5, lh + 0.5])
+        wx, wy = fwd[0, 0] * cx + fwd[0, 1] * cy + fwd[0, 2], fwd[1, 0] * cx + fwd[1, 1] * cy + fwd[1, 2]
+        slack = 1.01                                              # 1 px for the blur, 0.01 for the float32 matrix
+        win = [int(math.floor(wx.min() - 0.5 - slack)), int(math.floor(wy.min() - 0.5 - slack)),
+               int(math.ceil(wx.max() - 0.5 + slack)) + 1, int(math.ceil(wy.max() - 0.5 + slack)) + 1]
+        win = [min(max(win[0], 0), self.w), min(max(win[1], 0), self.h), min(max(win[2], 0), self.w), min(max(win[3], 0), self.h)]
+        row = np.zeros(ROW_WORDS, np.int32)
+        fl = row.view(np.float32)
+        row[0], row[1], row[2] = 1, lh, lw
+        row[3:7] = win
+        row[8:10] = np.array([off], np.int64).view(np.int32)
+        fl[10:16] = M[:2].reshape(-1).astype(np.float32)
+        fl[16:18] = np.float64(blur_weights(sigma)).astype(np.float32)
+        A, D, e = (np.eye(3), np.zeros((3, 3)), np.zeros(3)) if color is None else color
+        fl[18:27], fl[27:36], fl[36:39] = (np.asarray(A, np.float64).reshape(-1).astype(np.float32),
+                                           np.asarray(D, np.float64).reshape(-1).astype(np.float32), np.asarray(e, np.float64).astype(np.float32))
+        return row
+
+    def draw_params(self, batch, mode, pascal_rate=0.0, render_rate=1.0):
+        """render_host's draws, in its order and from the same np.random / random streams, without touching a pixel:
+        -> (labels (B,1,6+ncls) float32, rows (B, ROW_WORDS) int32).  Host only: needs neither torch nor a GPU.
+        Same seed, same decisions -- image by image, up to the paste offsets: their ranges come from the analytic box, a pixel
+        or two tighter than PIL's, and np.random.randint draws by rejection, so the number of raw values a paste draw takes
+        can differ between the two routes; from the first image where it does, a batch's streams have parted."""
+        if pascal_rate != 0.0 and not self.pascal_dataset[mode]:
+            raise ValueError('pascal_rate > 0 needs the PASCAL3D+ crops: RenderCar(..., pascal_root=...)')
+        labels = empty_labels(batch, self.num_cls)
+        rows = np.zeros((batch, ROW_WORDS), np.int32)
+        for i in range(batch):
+            if np.random.rand() > render_rate:
+                continue
+            r1 = np.random.uniform(low=0.9, high=1.1)
+            draw = self._draw_pascal if np.random.rand() < pascal_rate else self._draw_png
+            s, scale, to_sprite, l, t, r_, b, r, img_cls, dist, sigma = draw(mode, r1)
+            (xlo, xhi), (ylo, yhi) = paste_range(l, t, r_, b, self.h, self.w)
+            paste_x = np.random.randint(low=xlo, high=xhi)
+            paste_y = np.random.randint(low=ylo, high=yhi)
+            color = self.augs.affine() if self.augs is not None else None
+            rows[i] = self.param_row(s, scale, to_sprite, paste_x, paste_y, sigma, color)
+            labels[i] = car_label(img_cls, l, t, r_, b, paste_x, paste_y, r, dist, self.h, self.w)
+        return labels, rows
+
+    def render_device(self, bg, mode, pascal_rate=0.0, render_rate=1.0, out=None):
+        """render() with the pixels made on the device: bg (B,3,H,W) float32 0..255 CUDA tensor -> (images 0..1, labels), both
+        on the device.  The host draws the parameter rows (draw_params); rows and labels go up in ONE pinned, non-blocking
+        copy; yolo_render_stats takes each canvas's mean colour (what the contrast stage needs), yolo_render_cars samples the
+        resident atlas, colours and blends.  Runs on the current stream and does not synchronise."""
+        import torch
+        from . import lib as L
+        lib = L.load()
+        B = len(bg)
+        if tuple(bg.shape) != (B, 3, self.h, self.w) or bg.dtype != torch.float32 or not bg.is_cuda:
+            raise ValueError('bg should be a float32 CUDA tensor of shape (B, 3, %d, %d)' % (self.h, self.w))
+        dev = bg.device
+        L.require_current_device(dev, 'this render_device call')
+        bg = bg.contiguous()
+        if out is None:
+            out = torch.empty_like(bg)
+        elif tuple(out.shape) != tuple(bg.shape) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+            raise ValueError('out should be a contiguous float32 tensor of shape %r on %s' % (tuple(bg.shape), dev))
+        labels, rows = self.draw_params(B, mode, pascal_rate, render_rate)
+        state = self.__dict__.setdefault('_device_state', {})
+        if state.get('device') != dev:
+            state.clear()
+            state.update(device=dev, atlas=torch.from_numpy(self.atlas().data).to(dev), stage={}, work={})
+        nrow, nlab = rows.size * 4, labels.size * 4
+        slot = state['stage'].get(B)
+        if slot is None:
+            slot = state['stage'][B] = [torch.empty(nrow + nlab, dtype=torch.uint8, pin_memory=True), torch.cuda.Event()]
+        else:
+            slot[1].synchronize()         # the previous upload has left the staging buffer (waits for that copy only)
+        host = slot[0].numpy()
+        host[:nrow] = rows.reshape(-1).view(np.uint8)
+        host[nrow:] = labels.reshape(-1).view(np.uint8)
+        up = torch.empty(nrow + nlab, dtype=torch.uint8, device=dev)
+        up.copy_(slot[0], non_blocking=True)
+        slot[1].record()
+        work = state['work'].get(B)
+        if work is None:
+            nbytes = lib.yolo_render_workspace_bytes(B, self.h, self.w)
+            if nbytes <= 0:
+                raise L.YoloError('render_workspace_bytes failed with status %d' % nbytes)
+            work = state['work'][B] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        atlas = state['atlas']
+        L.check(lib.yolo_render_stats(L.ptr(atlas), atlas.numel(), L.ptr(up), L.ptr(work), B, self.h, self.w, L.stream_ptr()), 'render_stats')
+        L.check(lib.yolo_render_cars(L.ptr(bg), L.ptr(atlas), atlas.numel(), L.ptr(up), L.ptr(work), L.ptr(out), B, self.h, self.w,
+                                     L.stream_ptr()), 'render_cars')
+        return out, up[nrow:].view(torch.float32).view(B, 1, 6 + self.num_cls)
 
 
 # ---- LPGenerator.add (yolo_modules/licence_plate_render/__init__.py:21-166, 273-371): licence plates for CarLPNet ---------
