@@ -21,7 +21,8 @@ class YoloError(RuntimeError):
 
 
 def lab_knob(name, default=None):
-    """A/B and ablation switches of tools/ (YOLO_TRAIN_*, YOLO_SIDE_FILTER, ...): read ONLY when YOLO_LAB=1 is set -- the product
+    """A/B and ablation switches of tools/ (YOLO_TRAIN_BN3, YOLO_TRAIN_SERIAL_WGRAD, YOLO_TRAIN_NO_STATS_FUSION: train.py reads them once, in
+    Trainer.__init__): read ONLY when YOLO_LAB=1 is set -- the product
     does not change behaviour with the environment of whoever imports it (the C library's knobs are compiled out the same way:
     csrc/common.h YOLO_LAB_ENV).  Two deliberate exceptions stay plain: YOLO_AMD_LIB (which library to load) and the test-only
     switches of bench.py / GradBuckets.active (YOLO_BENCH_*)."""

@@ -2,13 +2,12 @@
 BatchNorm, target assignment (_find_best/_loss_mask), the five losses (_get_loss), backward of
 sum(losses), gradient all-reduce over ranks and the MXNet Adam update of trainer.step(batch_size).
 
-fp32 parity path: every op is a HIP kernel from libyolo_amd.so (bn_train.hip, wgrad.hip, train_ops.hip, loss.hip and the forward conv
-kernels re-used for the data gradient on flipped weights); torch owns memory, the stream and the
-process group only.  dtype 'bf16x3' (the split-bf16 path, include/yolo_amd.h YOLO_BF16X3) runs the same graph on (hi, lo) pairs:
-the fp32 arithmetic of the reference to ~16 significant bits at the bf16 MFMA rate.  One process per GPU; BN statistics stay local to the GPU (no SyncBN,
-car/YOLO.py:94-96).
+Three arithmetic paths, one graph: 'f32' (parity), 'bf16' (MFMA convolutions, statistics in the conv epilogue) and 'bf16x3' ((hi, lo)
+bf16 pairs: fp32 arithmetic to ~16 significant bits at the bf16 MFMA rate); master weights, BN statistics and Adam are fp32 on all three.
+Every op is a HIP kernel from libyolo_amd.so (bn_train.hip, wgrad.hip, train_ops.hip, loss.hip and the forward conv kernels re-used
+for the data gradient on flipped weights); torch owns memory, the stream and the process group only.  One process per GPU; BN
+statistics stay local to the GPU (no SyncBN, car/YOLO.py:94-96).
 """
-import os
 import ctypes as C
 
 import numpy as np
@@ -32,6 +31,19 @@ class _T(object):
         self.val, self.shape, self.grad, self.ready, self.ngot, self.gbuf = val, shape, None, False, 0, gbuf
 
 
+class _Prep(object):
+    """What one conv keeps between updates: its packed forward (`wp`) and data-gradient (`wd`, None: nothing is behind the layer)
+    weight images, `ones` / `bias` / `zeros` epilogue arrays of the padded channel count (the stem kernels and the output convs read
+    them; `bias` holds the layer's bias) and `s2`, the 2x2-window image of the sub-pixel data gradient (None: the dilated form)."""
+    __slots__ = ('wp', 'wd', 'ones', 'bias', 'zeros', 's2')
+
+
+class _Plan(object):
+    """The activations, descriptors and gradient buffers of one batch size; every field is set in Trainer._build."""
+    __slots__ = ('fwd', 'x8', 'stem_image', 'stem_or_conv', 'stem_rows', 'stem_part', 'stats_f', 'dil',
+                 'merged', 'dmerged', 'tot', 'AC', 'A', 'lp', 'dlp', 'lp_hw')
+
+
 class Trainer(object):
     def __init__(self, net, size, scale=None, learning_rate=1e-3, positive_weight=1.0, negative_weight=0.1,
                  car_rotate=False, beta1=0.9, beta2=0.999, eps=1e-8, lp_scale=None, lp_r_max=(45, 60, 45),
@@ -40,7 +52,7 @@ class Trainer(object):
         # 'bf16' halves the bytes per xGMI link, parallel.GradBuckets) and how many buckets the 492 MB buffer is cut into
         # dtype of activations and activation gradients: 'f32' (parity path), 'bf16' (MFMA bf16 convolutions,
         # transposing-read weight gradient) or 'bf16x3' (split pairs: the bf16x3 inference kernels for the forward and data
-        # gradient, yolo_conv_wgrad_split for the weight gradient); master weights, weight gradients, BN statistics and Adam are fp32.
+        # gradient, the split weight-gradient kernels); master weights, weight gradients, BN statistics and Adam are fp32.
         self.net, self.size = net, (int(size[0]), int(size[1]))
         self.tdt = torch.float32 if net.dtype == 'f32' else torch.bfloat16
         if net.dtype not in ('f32', 'bf16', 'bf16x3'):
@@ -94,8 +106,8 @@ class Trainer(object):
         # weights), and its folded / packed images are re-made on the next inference forward (net._version)
         net._plans = {}
         net._version += 1
-        self._prep = {}
-        self._prep_s2 = {}          # conv name -> (sub-pixel dgrad weight image, ones, zeros); see _dgrad
+        self._prep = {}             # conv name -> _Prep
+        self._s2_retired = []
         self._plans = {}
         self._dgrad_algo = {}
         self._wgrad_algo = {}
@@ -104,28 +116,29 @@ class Trainer(object):
             self._wgrad_algo.update(net._plan_state['wgrad'])
         self._fwd_B = None
         cmax = max(c.cout for c in g.convs())
-        # two BatchNorm workspaces used alternately (yolo_bn_train_*_pp: a call leaves its own dirty and zeroes the next one's)
+        # two BatchNorm workspaces used alternately (the *_pp BatchNorm entries: a call leaves its own dirty and zeroes the next one's)
         self.ws2 = [torch.zeros(2 * cmax, dtype=torch.float64, device=self.dev) for _ in range(2)]
         self._ws_i = 0
         self.probe = None         # a list: _backward appends (family, layer, elements, start event, end event) per BatchNorm backward call
-        self._bn3 = bool(L.lab_knob('YOLO_TRAIN_BN3'))      # (the knob: separate finalize launches, for A/B runs)
-        self.ws = torch.zeros(2 * cmax, dtype=torch.float64, device=self.dev)
+        # the lab knobs of this file (A/B runs of tools/; read here only, and only under YOLO_LAB=1): separate BatchNorm finalize
+        # launches; weight gradients in the serial order; BatchNorm sums in reduction passes of their own
+        self._bn3 = bool(L.lab_knob('YOLO_TRAIN_BN3'))
+        self._overlap = not L.lab_knob('YOLO_TRAIN_SERIAL_WGRAD')
+        # (the sums are otherwise taken in the producing convolution's epilogue, yolo_conv_desc.stats: bf16 only)
+        self._fuse_fwd = self.ldt == L.BF16 and not L.lab_knob('YOLO_TRAIN_NO_STATS_FUSION')
+        self.ws = torch.zeros(2 * cmax, dtype=torch.float64, device=self.dev) if self._bn3 else None
         wsf = self.lib.yolo_conv_wgrad_split_workspace_bytes if self.split else self.lib.yolo_conv_wgrad_workspace_bytes
         wsb = max(wsf(max(c.cin, 8), c.cout, c.k, self.ldt) for c in g.convs())
         self.wg_ws = torch.zeros(max(wsb, 16), dtype=torch.uint8, device=self.dev)       # (kept zeroed by the library)
         # weight gradients run on a side stream: they are off the backward pass's critical path (dy -> data gradient ->
         # previous layer's BN backward) and MFMA-bound, while the BN passes they overlap are HBM-bound
         self._side = torch.cuda.Stream(device=self.dev)
-        self._overlap = not L.lab_knob('YOLO_TRAIN_SERIAL_WGRAD')          # (the knob keeps the serial order for A/B runs)
-        # BatchNorm sums taken in the producing convolution's epilogue (yolo_conv_desc.stats) instead of in a reduction pass
-        # of their own; (the knob: the separate passes, for A/B runs)
-        self._fuse_stats = self.ldt == L.BF16 and not L.lab_knob('YOLO_TRAIN_NO_STATS_FUSION')
-        self._stats_b = None            # partial rows of the data gradients' statistics epilogues (grown on demand)
-        modes = L.lab_knob('YOLO_TRAIN_STATS_MODES', '1')    # '1' forward sums, '2' backward sums, '12' both
-        self._fuse_fwd, self._fuse_bwd = self._fuse_stats and '1' in modes, self._fuse_stats and '2' in modes
-        self._identity = not L.lab_knob('YOLO_TRAIN_UNIT_EPILOGUE')        # (the knob: scale 1 / bias 0 arrays instead of the identity epilogue)
         self._repack()
         self._packed_version = net._version
+
+    @property
+    def _measure(self):
+        return getattr(self.net, 'tune', None) == 'measure'
 
     def resized(self, size):
         """A Trainer for another image size with THIS one's hyper-parameters and optimiser state (Adam moments, update count):
@@ -140,48 +153,52 @@ class Trainer(object):
 
     # ---- weight images for the forward and data-gradient convolutions (re-packed after every update) ----
     def _repack(self):
-        """Forward and data-gradient weight images of every conv, re-packed after each update in ONE launch
-        (yolo_pack_conv_weights_batch) over a device-resident table built on first use."""
+        """Forward and data-gradient weight images of every conv, re-packed after each update; the bias arrays follow."""
+        (self._repack_split if self.split else self._repack_dense)()
+        for c in self.net.graph.convs():
+            if not c.bn:
+                self._prep[c.name].bias[:c.cout].copy_(self.pview[c.name + '.bias'])
+
+    def _new_prep(self, c, wp_bytes, wd_bytes):
+        """The _Prep record of conv c with zero-filled images of the given sizes (the pack kernels never write the images' padding
+        rows; wd_bytes None: no data-gradient image)."""
+        z = lambda n, dt=torch.float32: torch.zeros(n, dtype=dt, device=self.dev)
+        r = self._prep[c.name] = _Prep()
+        r.wp, r.wd, r.s2 = z(wp_bytes, torch.uint8), (z(wd_bytes, torch.uint8) if wd_bytes is not None else None), None
+        cp = self.lib.yolo_padded_channels(max(c.cout, c.cin))
+        r.ones, r.bias, r.zeros = z(cp), z(cp), z(cp)
+        r.ones[:max(c.cout, c.cin)] = 1.0
+        return r
+
+    def _repack_dense(self):
+        """ONE launch (yolo_pack_conv_weights_batch; bf16: yolo_pack_conv_weights_pairs, both images from one read of the weights)
+        over a device-resident table built on first use."""
         lib, st = self.lib, L.stream_ptr()
-        if self.split:
-            self._repack_split()
-            return
         if not self._prep:
-            items = np.zeros(0, dtype=[('w', '<u8'), ('packed', '<u8'), ('cout', '<i4'), ('cin', '<i4'), ('k', '<i4'), ('dgrad', '<i4')])
+            item_dt = np.dtype([('w', '<u8'), ('packed', '<u8'), ('cout', '<i4'), ('cin', '<i4'), ('k', '<i4'), ('dgrad', '<i4')])
+            pair_dt = np.dtype([('w', '<u8'), ('fwd', '<u8'), ('dgrad', '<u8'), ('cout', '<i4'), ('cin', '<i4'), ('k', '<i4'), ('r', '<i4')])
             recs, first = [], [0]
             pairs, pfirst = [], [0]
-            pair_dt = np.dtype([('w', '<u8'), ('fwd', '<u8'), ('dgrad', '<u8'), ('cout', '<i4'), ('cin', '<i4'), ('k', '<i4'), ('r', '<i4')])
             for c in self.net.graph.convs():
                 w = self.pview[c.name + '.weight']
-                # (zero-filled: the pair kernel never writes the images' padding rows)
-                wp = torch.zeros(lib.yolo_packed_weight_bytes(c.cout, c.cin, c.k, self.ldt), dtype=torch.uint8, device=self.dev)
-                wd = torch.zeros(lib.yolo_packed_weight_bytes(c.cin, c.cout, c.k, self.ldt), dtype=torch.uint8, device=self.dev)
-                cp = lib.yolo_padded_channels(max(c.cout, c.cin))
-                ones = torch.zeros(cp, dtype=torch.float32, device=self.dev); ones[:max(c.cout, c.cin)] = 1.0
-                bias = torch.zeros(cp, dtype=torch.float32, device=self.dev)
-                self._prep[c.name] = (wp, wd, ones, bias, torch.zeros(cp, dtype=torch.float32, device=self.dev))
-                nb = lib.yolo_pack_pair_blocks(c.cout, c.cin, c.k) if (self.ldt == L.BF16 and not L.lab_knob('YOLO_TRAIN_OLD_PACK')) else -1
+                r = self._new_prep(c, lib.yolo_packed_weight_bytes(c.cout, c.cin, c.k, self.ldt),
+                                   lib.yolo_packed_weight_bytes(c.cin, c.cout, c.k, self.ldt))
+                nb = lib.yolo_pack_pair_blocks(c.cout, c.cin, c.k) if self.ldt == L.BF16 else -1
                 if nb > 0:
-                    # both images from one read of the weights (yolo_pack_conv_weights_pairs)
-                    pairs.append((w.data_ptr(), wp.data_ptr(), wd.data_ptr(), c.cout, c.cin, c.k, 0))
+                    pairs.append((w.data_ptr(), r.wp.data_ptr(), r.wd.data_ptr(), c.cout, c.cin, c.k, 0))
                     pfirst.append(pfirst[-1] + nb)
                 else:
                     # (the dgrad record carries the arguments of yolo_pack_conv_weights_dgrad after its swap: rows = Cin_f)
-                    recs.append((w.data_ptr(), wp.data_ptr(), c.cout, c.cin, c.k, 0))
+                    recs.append((w.data_ptr(), r.wp.data_ptr(), c.cout, c.cin, c.k, 0))
                     first.append(first[-1] + lib.yolo_pack_batch_blocks(c.cout, c.cin, c.k, self.ldt))
-                    recs.append((w.data_ptr(), wd.data_ptr(), c.cin, c.cout, c.k, 1))
+                    recs.append((w.data_ptr(), r.wd.data_ptr(), c.cin, c.cout, c.k, 1))
                     first.append(first[-1] + lib.yolo_pack_batch_blocks(c.cin, c.cout, c.k, self.ldt))
-                if (c.k == 3 and c.stride == 2 and self.ldt == L.BF16 and c.cin % 8 == 0 and c.cout % 32 == 0
-                        and not L.lab_knob('YOLO_TRAIN_DILATED_DGRAD')):      # (the knob keeps the old form for A/B runs)
+                if c.k == 3 and c.stride == 2 and self.ldt == L.BF16 and c.cin % 8 == 0 and c.cout % 32 == 0:
                     # sub-pixel data gradient (yolo_conv_dgrad_s2): 2x2-window image with 4 x Cin_f output channels
-                    w2 = torch.empty(lib.yolo_packed_weight_bytes(4 * c.cin, c.cout, 2, self.ldt), dtype=torch.uint8, device=self.dev)
-                    cp4 = lib.yolo_padded_channels(4 * c.cin)
-                    ones4 = torch.zeros(cp4, dtype=torch.float32, device=self.dev); ones4[:4 * c.cin] = 1.0
-                    self._prep_s2[c.name] = (w2, ones4, torch.zeros(cp4, dtype=torch.float32, device=self.dev))
-                    recs.append((w.data_ptr(), w2.data_ptr(), 4 * c.cin, c.cout, 2, 2))
+                    r.s2 = torch.empty(lib.yolo_packed_weight_bytes(4 * c.cin, c.cout, 2, self.ldt), dtype=torch.uint8, device=self.dev)
+                    recs.append((w.data_ptr(), r.s2.data_ptr(), 4 * c.cin, c.cout, 2, 2))
                     first.append(first[-1] + lib.yolo_pack_batch_blocks(4 * c.cin, c.cout, 2, self.ldt))
-            items = np.array(recs, dtype=items.dtype)
-            self._pack_items = torch.from_numpy(items.view(np.uint8).copy()).to(self.dev)
+            self._pack_items = torch.from_numpy(np.array(recs, dtype=item_dt).view(np.uint8).copy()).to(self.dev)
             self._pack_first = torch.tensor(first, dtype=torch.int64, device=self.dev)
             self._pack_n, self._pack_blocks = len(recs), first[-1]
             self._pair_n, self._pair_blocks = len(pairs), pfirst[-1]
@@ -194,9 +211,6 @@ class Trainer(object):
         if self._pair_n:
             L.check(lib.yolo_pack_conv_weights_pairs(L.ptr(self._pair_items), L.ptr(self._pair_first), self._pair_n,
                                                      self._pair_blocks, st), 'pack pairs')
-        for c in self.net.graph.convs():
-            if not c.bn:
-                self._prep[c.name][3][:c.cout].copy_(self.pview[c.name + '.bias'])
 
     def _repack_split(self):
         """Split path: the forward and data-gradient images of every conv, per conv (yolo_pack_batch_blocks has no split form).
@@ -213,14 +227,9 @@ class Trainer(object):
                 #  does not take the layer --, no data-gradient image: nothing is behind the stem)
                 cip = c.cin if c.cin % 8 == 0 else (c.cin + 7) // 8 * 8
                 win = torch.zeros((c.cout, cip, c.k, c.k), dtype=torch.float32, device=self.dev) if cip != c.cin else None
-                wp = torch.zeros(lib.yolo_packed_weight_bytes(c.cout, cip, c.k, self.ldt), dtype=torch.uint8, device=self.dev)
-                wd = (torch.zeros(lib.yolo_packed_weight_bytes(c.cin, cof, c.k, self.ldt), dtype=torch.uint8, device=self.dev)
-                      if win is None else None)
-                cp = lib.yolo_padded_channels(max(c.cout, c.cin))
-                ones = torch.zeros(cp, dtype=torch.float32, device=self.dev); ones[:max(c.cout, c.cin)] = 1.0
-                bias = torch.zeros(cp, dtype=torch.float32, device=self.dev)
-                self._prep[c.name] = (wp, wd, ones, bias, torch.zeros(cp, dtype=torch.float32, device=self.dev))
-                self._split_items.append((c, w, wpad, cof, win, cip, wp, wd))
+                r = self._new_prep(c, lib.yolo_packed_weight_bytes(c.cout, cip, c.k, self.ldt),
+                                   lib.yolo_packed_weight_bytes(c.cin, cof, c.k, self.ldt) if win is None else None)
+                self._split_items.append((c, w, wpad, cof, win, cip, r.wp, r.wd))
         for c, w, wpad, cof, win, cip, wp, wd in self._split_items:
             if win is not None:
                 win[:, :c.cin].copy_(w)
@@ -232,24 +241,51 @@ class Trainer(object):
                 wpad[:c.cout].copy_(w)
                 src = wpad
             L.check(lib.yolo_pack_conv_weights_dgrad(L.ptr(src), L.ptr(wd), cof, c.cin, c.k, self.ldt, st), 'pack dgrad ' + c.name)
-        for c in self.net.graph.convs():
-            if not c.bn:
-                self._prep[c.name][3][:c.cout].copy_(self.pview[c.name + '.bias'])
 
-    # ---- plan ---------------------------------------------------------------------------------------------
+    # ---- buffers: the ONE place that knows who owns a gradient buffer -------------------------------------------
+    # Split path: the plan owns every activation and gradient buffer, zeroed once (the kernels never write the pad channels of
+    # the pair storage, which the convolutions read as operands of zero weights) -- NOTHING is allocated per step.  Dense
+    # paths: activations are plan-owned, gradients are fresh torch.empty tensors of the caching allocator.
     def _buf(self, shape):
-        """An activation-shaped buffer (N, H, W, C).  Split path: the dense pair storage (N, H, W, 2, round_up(C, 32)), ZEROED --
-        the kernels never write the pad channels, which the convolutions read as operands of zero weights."""
+        """An activation-shaped buffer (N, H, W, C).  Split path: the dense pair storage (N, H, W, 2, round_up(C, 32)), ZEROED."""
         if not self.split:
             return torch.empty(shape, dtype=self.tdt, device=self.dev)
         cp = -(-shape[-1] // 32) * 32
         return torch.zeros(tuple(shape[:-1]) + (2, cp), dtype=self.tdt, device=self.dev)
 
-    def _new(self, shape):
-        if self.split:
-            return _T(self._buf(shape), tuple(shape), gbuf=self._buf(shape))
-        return _T(torch.empty(shape, dtype=self.tdt, device=self.dev), tuple(shape))
+    def _new(self, shape, grad=True):
+        """A plan activation; split path: with the buffer of its gradient's first contribution (grad=False: it receives none)."""
+        return _T(self._buf(shape), tuple(shape), gbuf=self._buf(shape) if (self.split and grad) else None)
 
+    def _zeroed(self, shape):
+        """A zeroed activation-shaped scratch buffer (timing runs only)."""
+        return self._buf(shape) if self.split else torch.zeros(shape, dtype=self.tdt, device=self.dev)
+
+    def _grad_out(self, t):
+        """Where the first contribution to d(loss)/d(t) is written."""
+        return t.gbuf if self.split else torch.empty(t.shape, dtype=self.tdt, device=self.dev)
+
+    def _dy_for(self, op, poison=False):
+        """d(loss)/d(yraw) of a conv_bn op (poison -- diagnostics, dense paths: an element the kernel does not write must show)."""
+        if self.split:
+            return op['dy']
+        dy = torch.empty(op['yraw'].shape, dtype=self.tdt, device=self.dev)
+        if poison:
+            dy.fill_(float('nan'))
+        return dy
+
+    def _dilated_for(self, c, shape):
+        """The zero-dilated copy of a stride-2 conv's output gradient."""
+        return self._P.dil[c.name] if self.split else torch.empty(shape, dtype=self.tdt, device=self.dev)
+
+    def _captured(self, t, cout, copy):
+        """A gradient as _backward's `capture` hands it out.  Split path: the values hi + lo as an fp32 (N, H, W, C) copy (the pair
+        buffers are plan-owned, and the next step overwrites them)."""
+        if self.split:
+            return t[..., 0, :cout].float() + t[..., 1, :cout].float()
+        return t.clone() if copy else t
+
+    # ---- plan ---------------------------------------------------------------------------------------------
     def _conv_desc(self, x, xshape, wp, scale, bias, y, cin, cout, k, stride, residual=None, out_f32=0, y_bs=0, y_ps=0):
         d = L.ConvDesc()
         d.x, d.w_packed, d.scale, d.bias = L.ptr(x), L.ptr(wp), L.ptr(scale), L.ptr(bias)
@@ -263,28 +299,35 @@ class Trainer(object):
     def _tune(self, d):
         """Pick the conv variant by measurement when the net was built with tune='measure' (the timing runs only
         overwrite d.y, which nothing has consumed yet)."""
-        if getattr(self.net, 'tune', None) == 'measure':
+        if self._measure:
             d.algo = self.net._measure_algo(d)
 
     def _build(self, B, H, W):
-        g = self.net.graph
-        P = type('Plan', (), {})()
-        P.fwd, P.tensors = [], []
-        P.stats_floats = 0
-        # (the 8-channel image copy: the stem's input, which receives no gradient -- no gradient buffer on the split path)
-        P.x8 = _T(self._buf((B, H, W, 8)), (B, H, W, 8)) if self.split else self._new((B, H, W, 8))
+        g, lib = self.net.graph, self.lib
+        P = _Plan()
+        P.fwd = []
+        stats_floats = 0
+        P.x8 = self._new((B, H, W, 8), grad=False)           # the 8-channel image copy: the stem's input, which receives no gradient
+        # the stem runs as a kernel of the inference path on the NCHW image (identity scale/bias, linear: raw y) -- bf16: the fused
+        # one; split: the split one, and a stem that one does not take (Cout) runs as a convolution of the 8-channel image copy
+        c = g.stem
+        P.stem_or_conv = self.split and c.cin == 3
+        P.stem_image = P.stem_or_conv or (self.ldt == L.BF16 and c.cin == 3 and c.cout % 4 == 0 and c.cout <= 64)
+        # the stem's batch sums are taken in the kernel too (the largest reduction pass of the step)
+        P.stem_rows = lib.yolo_stem_stats_rows(B, H, W, c.cout) if (self._fuse_fwd and P.stem_image) else -1
+        P.stem_part = torch.empty(P.stem_rows * 2 * c.cout, dtype=torch.float32, device=self.dev) if P.stem_rows > 0 else None
 
         def conv_bn(c, xin, residual=None):
+            nonlocal stats_floats
             N, Hh, Ww, Cc = xin.shape
             ho, wo = c.out_hw(Hh, Ww)
             yraw, z = self._new((N, ho, wo, c.cout)), self._new((N, ho, wo, c.cout))
             mean = torch.empty(c.cout, dtype=torch.float32, device=self.dev)
             invstd = torch.empty_like(mean)
-            wp, wd, ones, bias, zeros = self._prep[c.name]
-            ident = (None, None) if self._identity else (ones, zeros)     # raw convolution: identity epilogue
-            d = self._conv_desc(xin.val, xin.shape, wp, ident[0], ident[1], yraw.val, Cc, c.cout, c.k, c.stride)
+            # raw convolution: identity epilogue
+            d = self._conv_desc(xin.val, xin.shape, self._prep[c.name].wp, None, None, yraw.val, Cc, c.cout, c.k, c.stride)
             self._tune(d)
-            op = dict(kind='conv_bn', c=c, x=xin, yraw=yraw, z=z, mean=mean, invstd=invstd, res=residual, desc=d, srows=0, brows=0)
+            op = dict(kind='conv_bn', c=c, x=xin, yraw=yraw, z=z, mean=mean, invstd=invstd, res=residual, desc=d, srows=0)
             if self.split:
                 # the plan owns every gradient buffer of the split path: d(loss)/d(yraw) and, for a stride-2 conv, its dilated copy
                 op['dy'] = yraw.gbuf
@@ -294,14 +337,22 @@ class Trainer(object):
             #  channel -- the epilogue's plain fp32 partial sums lose digits when a few nearly equal values make mean^2 >> variance)
             if self._fuse_fwd and not (c is g.stem) and N * ho * wo >= 4096 and self._pipe_kernel(d):
                 d.stats, d.stats_mode = 1, 1                      # (any non-NULL pointer for the query)
-                rows = self.lib.yolo_conv_stats_rows(C.byref(d))
+                rows = lib.yolo_conv_stats_rows(C.byref(d))
                 if rows > 0:
                     op['srows'] = rows
-                    P.stats_floats = max(P.stats_floats, rows * 2 * self.lib.yolo_padded_channels(c.cout))
+                    stats_floats = max(stats_floats, rows * 2 * lib.yolo_padded_channels(c.cout))
                 else:
                     d.stats, d.stats_mode = None, 0
             P.fwd.append(op)
             return z
+
+        def out_conv(c, t, hw_, y, src, y_bs=0, y_ps=0):
+            # an output conv writes fp32 logits at y; src: its slice of d(loss)/d(logits) as (pointer, batch stride, pixel stride)
+            r = self._prep[c.name]
+            d = self._conv_desc(t.val, t.shape, r.wp, r.ones, r.bias, y, c.cin, c.cout, 1, 1, out_f32=1, y_bs=y_bs, y_ps=y_ps)
+            self._tune(d)
+            cpad = (c.cout + 7) // 8 * 8
+            P.fwd.append(dict(kind='out', c=c, x=t, desc=d, hw=hw_, cpad=cpad, src=src, dyp=self._buf((B * hw_, cpad))))
 
         x = conv_bn(g.stem, P.x8)
         routes = []
@@ -320,7 +371,7 @@ class Trainer(object):
         P.merged = torch.empty((B, tot, AC), dtype=torch.float32, device=self.dev)
         P.dmerged = torch.empty_like(P.merged)
         P.tot, P.AC, P.A = tot, AC, A
-        P.lp = P.dlp = None
+        P.lp = P.dlp = P.lp_hw = None
         for i, (body, tip, outc, nA) in enumerate(g.heads):
             if g.lp_out is not None and i >= len(g.heads) - 1:
                 # CarLPNet's LP branch (car_and_LP/YOLO.py:72-79): reads the input of the finest detection block
@@ -332,27 +383,15 @@ class Trainer(object):
                 hw_lp = t.shape[1] * t.shape[2]
                 P.lp = torch.empty((B, hw_lp, lc.cout), dtype=torch.float32, device=self.dev)
                 P.dlp = torch.empty_like(P.lp)
-                wp, wd, ones, bias, zeros = self._prep[lc.name]
-                d = self._conv_desc(t.val, t.shape, wp, ones, bias, P.lp.data_ptr(), lc.cin, lc.cout, 1, 1, out_f32=1)
-                self._tune(d)
-                cpad = (lc.cout + 7) // 8 * 8
-                P.fwd.append(dict(kind='out', c=lc, x=t, desc=d, hw=hw_lp, cpad=cpad,
-                                  src=(P.dlp.data_ptr(), hw_lp * lc.cout, lc.cout),
-                                  dyp=self._buf((B * hw_lp, cpad))))
+                out_conv(lc, t, hw_lp, P.lp.data_ptr(), (P.dlp.data_ptr(), hw_lp * lc.cout, lc.cout))
                 P.lp_hw = (t.shape[1], t.shape[2])
             for c in body:
                 x = conv_bn(c, x)
             route = x
             t = conv_bn(tip, route)
             k = len(g.heads) - 1 - i
-            wp, wd, ones, bias, zeros = self._prep[outc.name]
-            yptr = P.merged.data_ptr() + offs[k] * AC * 4
-            d = self._conv_desc(t.val, t.shape, wp, ones, bias, yptr, outc.cin, outc.cout, 1, 1, out_f32=1, y_bs=tot * AC, y_ps=AC)
-            self._tune(d)
-            cpad = (outc.cout + 7) // 8 * 8
-            P.fwd.append(dict(kind='out', c=outc, x=t, desc=d, hw=hw[k], cpad=cpad,
-                              src=(P.dmerged.data_ptr() + offs[k] * AC * 4, tot * AC, AC),
-                              dyp=self._buf((B * hw[k], cpad))))
+            out_conv(outc, t, hw[k], P.merged.data_ptr() + offs[k] * AC * 4, (P.dmerged.data_ptr() + offs[k] * AC * 4, tot * AC, AC),
+                     y_bs=tot * AC, y_ps=AC)
             if i >= len(g.heads) - 1:
                 break
             x = conv_bn(g.transitions[i], route)
@@ -362,19 +401,10 @@ class Trainer(object):
             x = cat
         P.dil = {op['c'].name: op['dil'] for op in P.fwd if 'dil' in op}      # (split path: the plan-owned dilated gradients)
         # forward statistics partials: one buffer, consumed by the BatchNorm call right behind each convolution
-        P.stats_f = torch.empty(max(P.stats_floats, 4), dtype=torch.float32, device=self.dev)
+        P.stats_f = torch.empty(max(stats_floats, 4), dtype=torch.float32, device=self.dev)
         for op in P.fwd:
             if op['kind'] == 'conv_bn' and op['srows']:
                 op['desc'].stats = L.ptr(P.stats_f)
-        # which layer produced a tensor, and how many gradient contributions it will receive (its consumers)
-        P.prod, P.nuse = {}, {}
-        for op in P.fwd:
-            if op['kind'] == 'conv_bn':
-                P.prod[id(op['z'])] = op
-            for k in ('x', 'res', 'up', 'route'):
-                t = op.get(k)
-                if t is not None:
-                    P.nuse[id(t)] = P.nuse.get(id(t), 0) + 1
         return P
 
     def _pipe_kernel(self, d):
@@ -383,78 +413,118 @@ class Trainer(object):
         return self.lib.yolo_conv_kernel_name(C.byref(d), buf, 256) == 0 and any(
             k in buf.value for k in (b'conv_pipe_kernel', b'conv_igemm_kernel', b'conv_stream_kernel'))
 
+    # ---- the call sites of the library's entry families -------------------------------------------------------------
     def _next_ws(self):
-        """(this call's BatchNorm workspace -- zero --, the one it zeroes for the next call)."""
+        """(this call's BatchNorm workspace -- zero --, the one it zeroes for the next call, their size)."""
         a, b = self.ws2[self._ws_i], self.ws2[self._ws_i ^ 1]
         self._ws_i ^= 1
-        return L.ptr(a), L.ptr(b)
+        return L.ptr(a), L.ptr(b), a.numel()
+
+    def _bn_fwd(self, op, st, partials=None, rows=0, cpad=0):
+        """Train-mode BatchNorm + leaky ReLU (+ residual) of a conv_bn op: z from yraw.  partials: `rows` rows of batch sums of
+        channel pitch `cpad` that the producing kernel's epilogue took (the stem kernel, a convolution with desc.stats)."""
+        lib, c, y, p = self.lib, op['c'], op['yraw'], self.net.params
+        io = (L.ptr(y.val), L.ptr(p[c.name + '.gamma']), L.ptr(p[c.name + '.beta']),
+              L.ptr(op['res'].val) if op['res'] is not None else None, L.ptr(op['z'].val), L.ptr(op['mean']), L.ptr(op['invstd']),
+              L.ptr(p[c.name + '.running_mean']), L.ptr(p[c.name + '.running_var']))
+        tail = (y.shape[0] * y.shape[1] * y.shape[2], c.cout, BN_EPS, BN_MOMENTUM, LEAKY_SLOPE, self.ldt, st)
+        if partials is not None:
+            L.check(lib.yolo_bn_train_fwd_partials(L.ptr(partials), rows, cpad, *io, *self._next_ws(), *tail), 'bn (partials) ' + c.name)
+        elif self._bn3:
+            L.check(lib.yolo_bn_train_fwd(*io, L.ptr(self.ws), *tail), 'bn ' + c.name)
+        else:
+            L.check(lib.yolo_bn_train_fwd_pp(*io, *self._next_ws(), *tail), 'bn ' + c.name)
+
+    def _bn_bwd(self, op, dz, dy, st):
+        """dy = d(loss)/d(yraw) from dz = d(loss)/d(z), and the layer's gamma / beta gradients."""
+        lib, c, y, p = self.lib, op['c'], op['yraw'], self.net.params
+        npix = y.shape[0] * y.shape[1] * y.shape[2]
+        io = (L.ptr(dz), L.ptr(y.val), L.ptr(op['mean']), L.ptr(op['invstd']), L.ptr(p[c.name + '.gamma']), L.ptr(p[c.name + '.beta']),
+              L.ptr(dy), L.ptr(self.gview[c.name + '.gamma']), L.ptr(self.gview[c.name + '.beta']))
+        tail = (npix, c.cout, LEAKY_SLOPE, self.ldt, st)
+        if self._bn3:
+            L.check(lib.yolo_bn_train_bwd(*io, L.ptr(self.ws), *tail), 'bn bwd ' + c.name)
+            return
+        ws = self._next_ws()
+        pr = self.probe
+        if pr is not None:                  # (measurement only, bench.py's training roofline: HIP events around the call)
+            e0 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+        L.check(lib.yolo_bn_train_bwd_pp(*io, *ws, *tail), 'bn bwd ' + c.name)
+        if pr is not None:
+            e1 = torch.cuda.Event(enable_timing=True)
+            e1.record()
+            pr.append(('bn_bwd', c.name, npix * c.cout, e0, e1))
+
+    def _wgrad_launch(self, dy, x, dw, N, H, W, Cx, cout, k, stride, row=0, lo=0, algo=None):
+        """launch(stream) -> status: the weight gradient dw (fp32) of a (k, stride) conv from dy and x (N, H, W, Cx).  row / lo: the
+        element stride between dy's pixels and the offset of their lo plane (0: dense).  algo None: the library's own entry
+        (the entry that takes an id otherwise); the split path has one entry, whose id 0 is the library's choice."""
+        lib, ws = self.lib, self.wg_ws
+
+        def launch(s):
+            a = (L.ptr(dy), L.ptr(x), L.ptr(dw), N, H, W, Cx, cout, k, stride)
+            if self.split:
+                return lib.yolo_conv_wgrad_split(*a, row, lo, self.ldt, L.ptr(ws), algo or 0, s)
+            if algo is None:
+                return lib.yolo_conv_wgrad(*a, row, self.ldt, L.ptr(ws), s)
+            return lib.yolo_conv_wgrad_algo(*a, row, self.ldt, L.ptr(ws), algo, s)
+        return launch
+
+    def _wgrad_algos(self, c):
+        """The algo ids _wgrad_launch takes for conv c, the library's choice (0) first."""
+        if self.split:
+            return (0, 1, 2)                          # the library's choice, 64 x 64, 128 x 128 tiles
+        return (0, 2, 3, 4) if (c.k == 3 and c.stride == 1) else (0, 1, 5) if c.k == 1 else (0,)
+
+    def _out_pitch(self, cpad):
+        """(row stride, lo offset) of an output conv's gathered gradient rows of cpad channels; split path: dense pair rows, planes of
+        round_up(cpad, 32)."""
+        if not self.split:
+            return cpad, 0
+        scp = -(-cpad // 32) * 32
+        return 2 * scp, scp
+
+    def _bias_grad(self, dyp, db, rows, cout, cpad, st):
+        # (split rows: the library derives the pitch from the channel count)
+        L.check(self.lib.yolo_bias_grad(L.ptr(dyp), L.ptr(db), rows, cout, 0 if self.split else cpad, self.ldt, st), 'db')
+
+    def _add(self, dst, src, shape, st):
+        """dst += src, two gradients of an activation of `shape`."""
+        if self.split:
+            N, Hh, Ww, Cc = shape
+            L.check(self.lib.yolo_add_split(L.ptr(dst), L.ptr(src), L.ptr(dst), N * Hh * Ww, Cc, self.ldt, st), 'add')
+        else:
+            L.check(self.lib.yolo_add(L.ptr(dst), L.ptr(src), L.ptr(dst), src.numel(), self.ldt, st), 'add')
 
     # ---- forward (train mode) -----------------------------------------------------------------------------
     def _forward(self, P, images):
         lib, st = self.lib, L.stream_ptr()
         B, _, H, W = images.shape
+        g = self.net.graph
         L.check(lib.yolo_nchw_to_nhwc(images.data_ptr(), L.ptr(P.x8.val), B, 3, H, W, 8, self.ldt, st), 'nchw_to_nhwc')
         for op in P.fwd:
             if op['kind'] == 'conv_bn':
                 c = op['c']
-                y, z = op['yraw'], op['z']
-                g = self.net.graph
-                if c is g.stem and self.ldt == L.BF16 and c.cin == 3 and c.cout % 4 == 0 and c.cout <= 64:
-                    # the fused NCHW-image stem kernel of the inference path (identity scale/bias, linear): raw y
-                    wp, wd, ones, bias, zeros = self._prep[c.name]
-                    rows = lib.yolo_stem_stats_rows(B, H, W, c.cout) if self._fuse_fwd else -1
-                    if rows > 0:
-                        # the stem's batch sums are taken in the kernel too (the largest reduction pass of the step)
-                        if getattr(P, 'stem_part', None) is None:
-                            P.stem_part = torch.empty(rows * 2 * c.cout, dtype=torch.float32, device=self.dev)
-                        L.check(lib.yolo_stem_conv_fwd_stats(images.data_ptr(), L.ptr(self.pview[c.name + '.weight']), L.ptr(ones),
-                                                             L.ptr(zeros), L.ptr(y.val), B, H, W, 3, c.cout, self.ldt, 1.0,
-                                                             L.ptr(P.stem_part), st), 'stem')
-                        npix, p = B * H * W, self.net.params
-                        ws, wn = self._next_ws()
-                        L.check(lib.yolo_bn_train_fwd_partials(L.ptr(P.stem_part), rows, c.cout, L.ptr(y.val),
-                                                               L.ptr(p[c.name + '.gamma']), L.ptr(p[c.name + '.beta']), None,
-                                                               L.ptr(z.val), L.ptr(op['mean']), L.ptr(op['invstd']),
-                                                               L.ptr(p[c.name + '.running_mean']), L.ptr(p[c.name + '.running_var']),
-                                                               ws, wn, self.ws2[0].numel(), npix, c.cout, BN_EPS, BN_MOMENTUM,
-                                                               LEAKY_SLOPE, self.ldt, st), 'bn (stem partials)')
+                if c is g.stem and P.stem_image:
+                    r = self._prep[c.name]
+                    stem = (images.data_ptr(), L.ptr(self.pview[c.name + '.weight']), L.ptr(r.ones), L.ptr(r.zeros), L.ptr(op['yraw'].val),
+                            B, H, W, 3, c.cout, self.ldt, 1.0)
+                    if P.stem_part is not None:
+                        L.check(lib.yolo_stem_conv_fwd_stats(*stem, L.ptr(P.stem_part), st), 'stem')
+                        self._bn_fwd(op, st, P.stem_part, P.stem_rows, c.cout)
                         continue
-                    L.check(lib.yolo_stem_conv_fwd(images.data_ptr(), L.ptr(self.pview[c.name + '.weight']), L.ptr(ones),
-                                                   L.ptr(zeros), L.ptr(y.val), B, H, W, 3, c.cout, self.ldt, 1.0, st), 'stem')
-                else:
-                    rc = L.EUNSUPPORTED
-                    if c is g.stem and self.split and c.cin == 3:
-                        # the split stem kernel of the inference path on the NCHW image (identity scale/bias, linear): raw y;
-                        # a stem it does not take (Cout) runs as a convolution of the 8-channel image copy
-                        rc = lib.yolo_stem_conv_fwd(images.data_ptr(), L.ptr(self.pview[c.name + '.weight']), L.ptr(self._prep[c.name][2]),
-                                                    L.ptr(self._prep[c.name][4]), L.ptr(y.val), B, H, W, 3, c.cout, self.ldt, 1.0, st)
-                        if rc != L.EUNSUPPORTED:
-                            L.check(rc, 'stem')
-                    if rc == L.EUNSUPPORTED:
+                    rc = lib.yolo_stem_conv_fwd(*stem, st)
+                    if rc == L.EUNSUPPORTED and P.stem_or_conv:
                         L.check(lib.yolo_conv_fwd(C.byref(op['desc']), st), 'conv ' + c.name)
-                npix = y.shape[0] * y.shape[1] * y.shape[2]
-                p = self.net.params
-                if self._bn3:
-                    L.check(lib.yolo_bn_train_fwd(L.ptr(y.val), L.ptr(p[c.name + '.gamma']), L.ptr(p[c.name + '.beta']),
-                                                  L.ptr(op['res'].val) if op['res'] is not None else None, L.ptr(z.val),
-                                                  L.ptr(op['mean']), L.ptr(op['invstd']), L.ptr(p[c.name + '.running_mean']),
-                                                  L.ptr(p[c.name + '.running_var']), L.ptr(self.ws), npix, c.cout, BN_EPS,
-                                                  BN_MOMENTUM, LEAKY_SLOPE, self.ldt, st), 'bn ' + c.name)
-                    continue
-                ws, wn = self._next_ws()
-                if op['srows']:
-                    L.check(lib.yolo_bn_train_fwd_partials(L.ptr(P.stats_f), op['srows'], lib.yolo_padded_channels(c.cout),
-                                                           L.ptr(y.val), L.ptr(p[c.name + '.gamma']), L.ptr(p[c.name + '.beta']),
-                                                           L.ptr(op['res'].val) if op['res'] is not None else None, L.ptr(z.val),
-                                                           L.ptr(op['mean']), L.ptr(op['invstd']), L.ptr(p[c.name + '.running_mean']),
-                                                           L.ptr(p[c.name + '.running_var']), ws, wn, self.ws2[0].numel(), npix, c.cout,
-                                                           BN_EPS, BN_MOMENTUM, LEAKY_SLOPE, self.ldt, st), 'bn (partials) ' + c.name)
-                    continue
-                L.check(lib.yolo_bn_train_fwd_pp(L.ptr(y.val), L.ptr(p[c.name + '.gamma']), L.ptr(p[c.name + '.beta']),
-                                                 L.ptr(op['res'].val) if op['res'] is not None else None, L.ptr(z.val),
-                                                 L.ptr(op['mean']), L.ptr(op['invstd']), L.ptr(p[c.name + '.running_mean']),
-                                                 L.ptr(p[c.name + '.running_var']), ws, wn, self.ws2[0].numel(), npix, c.cout, BN_EPS,
-                                                 BN_MOMENTUM, LEAKY_SLOPE, self.ldt, st), 'bn ' + c.name)
+                    else:
+                        L.check(rc, 'stem')
+                else:
+                    L.check(lib.yolo_conv_fwd(C.byref(op['desc']), st), 'conv ' + c.name)
+                if op['srows'] and not self._bn3:
+                    self._bn_fwd(op, st, P.stats_f, op['srows'], lib.yolo_padded_channels(c.cout))
+                else:
+                    self._bn_fwd(op, st)
             elif op['kind'] == 'out':
                 L.check(lib.yolo_conv_fwd(C.byref(op['desc']), st), 'out conv')
             else:
@@ -468,32 +538,27 @@ class Trainer(object):
         t.ngot += 1
         if not t.ready:
             t.grad, t.ready = src, True
-        elif self.split:
-            N, Hh, Ww, Cc = t.shape
-            L.check(self.lib.yolo_add_split(L.ptr(t.grad), L.ptr(src), L.ptr(t.grad), N * Hh * Ww, Cc, self.ldt, L.stream_ptr()), 'add')
         else:
-            L.check(self.lib.yolo_add(L.ptr(t.grad), L.ptr(src), L.ptr(t.grad), src.numel(), self.ldt, L.stream_ptr()), 'add')
+            self._add(t.grad, src, t.shape, L.stream_ptr())
 
     def _dgrad(self, c, dy, dy_shape, xin, cin_of_dy):
-        """grad[xin] (+)= data gradient of conv c given dy (N,Ho,Wo,cin_of_dy) (dense)."""
+        """grad[xin] (+)= data gradient of conv c given dy (N,Ho,Wo,cin_of_dy) (dense).  Identity epilogues throughout."""
         lib, st = self.lib, L.stream_ptr()
-        wp, wd, ones, bias, zeros = self._prep[c.name]
+        r = self._prep[c.name]
         N, Hh, Ww, Cx = xin.shape
-        s2 = self._prep_s2.get(c.name) if c.stride == 2 else None
-        if s2 is not None and Hh == 2 * dy_shape[1] and Ww == 2 * dy_shape[2] and cin_of_dy == c.cout:
+        if r.s2 is not None and Hh == 2 * dy_shape[1] and Ww == 2 * dy_shape[2] and cin_of_dy == c.cout:
             # sub-pixel form: one 2x2-window conv over dy writes the four phases of dx (no dilated copy, 16/36 of the MFMAs)
             if not xin.ready:
                 out, resid = torch.empty(xin.shape, dtype=self.tdt, device=self.dev), None
             else:
                 out, resid = xin.grad, xin.grad
-            sb = (None, None) if self._identity else (s2[1], s2[2])
-            d = self._conv_desc(dy, dy_shape, s2[0], sb[0], sb[1], out, cin_of_dy, 4 * Cx, 2, 1, residual=resid)
+            d = self._conv_desc(dy, dy_shape, r.s2, None, None, out, cin_of_dy, 4 * Cx, 2, 1, residual=resid)
             rc = None
-            if getattr(self.net, 'tune', None) == 'measure':
+            if self._measure:
                 key = ('s2', dy_shape, cin_of_dy, Cx, resid is not None)
                 if key not in self._dgrad_algo:
                     scratch = torch.zeros(xin.shape, dtype=self.tdt, device=self.dev)
-                    dm = self._conv_desc(dy, dy_shape, s2[0], sb[0], sb[1], scratch, cin_of_dy, 4 * Cx, 2, 1,
+                    dm = self._conv_desc(dy, dy_shape, r.s2, None, None, scratch, cin_of_dy, 4 * Cx, 2, 1,
                                          residual=scratch if resid is not None else None)
                     self._dgrad_algo[key] = self.net._measure_algo(dm, fn=lib.yolo_conv_dgrad_s2, algos=(2, 6, 10, 4))
                 d.algo = self._dgrad_algo[key]
@@ -507,93 +572,61 @@ class Trainer(object):
                 return
             if rc != L.EUNSUPPORTED:
                 L.check(rc, 'dgrad_s2 ' + c.name)
-            del self._prep_s2[c.name]              # no variant fits this shape: the dilated form from now on
+            # no variant fits this shape: the dilated form from now on (the pack table goes on writing the image: it stays alive)
+            self._s2_retired.append(r.s2)
+            r.s2 = None
         if c.stride == 2:
-            dil = self._P.dil[c.name] if self.split else torch.empty((N, Hh, Ww, cin_of_dy), dtype=self.tdt, device=self.dev)
-            L.check(lib.yolo_dilate2x(L.ptr(dy), L.ptr(dil), N, Hh, Ww, dy_shape[1], dy_shape[2], cin_of_dy, self.ldt, st), 'dilate')
-            src, sshape = dil, (N, Hh, Ww, cin_of_dy)
+            src, sshape = self._dilated_for(c, (N, Hh, Ww, cin_of_dy)), (N, Hh, Ww, cin_of_dy)
+            L.check(lib.yolo_dilate2x(L.ptr(dy), L.ptr(src), N, Hh, Ww, dy_shape[1], dy_shape[2], cin_of_dy, self.ldt, st), 'dilate')
         else:
             src, sshape = dy, dy_shape
         if not xin.ready:
-            out = xin.gbuf if self.split else torch.empty(xin.shape, dtype=self.tdt, device=self.dev)
-            resid = None
+            out, resid = self._grad_out(xin), None
         else:
             out, resid = xin.grad, xin.grad
-        if self._identity:
-            ones = zeros = None
-        d = self._conv_desc(src, sshape, wd, ones, zeros, out, cin_of_dy, Cx, c.k, 1, residual=resid)
-        # this call completes d(loss)/d(xin): take the BatchNorm-backward sums of the layer that produced xin in the epilogue
-        P = self._P
-        prod = P.prod.get(id(xin)) if (self._fuse_bwd and c.stride == 1 and xin.ngot + 1 == P.nuse.get(id(xin), 0)) else None
-        if getattr(self.net, 'tune', None) == 'measure':
+        d = self._conv_desc(src, sshape, r.wd, None, None, out, cin_of_dy, Cx, c.k, 1, residual=resid)
+        if self._measure:
             key = self._key_tag + (sshape, cin_of_dy, Cx, c.k, resid is not None)
             if key not in self._dgrad_algo:
                 # time the variants on scratch outputs: the real `out` may already hold an accumulated gradient
-                scratch = self._buf(xin.shape) if self.split else torch.zeros(xin.shape, dtype=self.tdt, device=self.dev)
-                dm = self._conv_desc(src, sshape, wd, ones, zeros, scratch, cin_of_dy, Cx, c.k, 1,
+                scratch = self._zeroed(xin.shape)
+                dm = self._conv_desc(src, sshape, r.wd, None, None, scratch, cin_of_dy, Cx, c.k, 1,
                                      residual=scratch if resid is not None else None)
                 self._dgrad_algo[key] = self.net._measure_algo(dm)
             d.algo = self._dgrad_algo[key]
-        if prod is not None and self._pipe_kernel(d):
-            pc, pp = prod['c'], self.net.params
-            d.stats, d.stats_mode, d.stats_y = 1, 2, L.ptr(prod['yraw'].val)
-            d.stats_mean, d.stats_invstd = L.ptr(prod['mean']), L.ptr(prod['invstd'])
-            d.stats_gamma, d.stats_beta, d.stats_slope = L.ptr(pp[pc.name + '.gamma']), L.ptr(pp[pc.name + '.beta']), LEAKY_SLOPE
-            rows = lib.yolo_conv_stats_rows(C.byref(d))
-            if rows > 0:
-                need = rows * 2 * lib.yolo_padded_channels(Cx)
-                if self._stats_b is None or self._stats_b.numel() < need:
-                    self._stats_b = torch.empty(need, dtype=torch.float32, device=self.dev)
-                d.stats = L.ptr(self._stats_b)
-                prod['brows'] = rows
-            else:
-                d.stats, d.stats_mode = None, 0
         L.check(lib.yolo_conv_fwd(C.byref(d), st), 'dgrad ' + c.name)
         xin.grad, xin.ready = out, True
         xin.ngot += 1
 
-    def _wgrad_tag(self, c, cin):
-        """Which weight-gradient kernel serves conv c ('walk' = csrc/wgrad_walk.hip); only YOLO_SIDE_FILTER (diagnostics:
-        the classes that go to the side stream) looks at it."""
-        if self.ldt == L.BF16 and c.k == 3 and c.stride == 1 and cin % 64 == 0 and c.cout % 64 == 0:
-            return 'walk'
-        return 'k%ds%d' % (c.k, c.stride)
-
     def _wgrad_algo_for(self, c, dy, xin):
-        """yolo_conv_wgrad_algo id for conv c: 0 (the library's choice) unless the net was built with tune='measure' -- then the
+        """Weight-gradient algo id for conv c: 0 (the library's choice) unless the net was built with tune='measure' -- then the
         fastest of the kernels that take the shape, timed once per layer shape on a scratch gradient (the 8-wave row walk wins
         on two D53 shapes, the 16-column walker on the 13x13 ones, ...)."""
-        if getattr(self.net, 'tune', None) != 'measure' or self.ldt == L.F32 or L.lab_knob('YOLO_TRAIN_NO_WGRAD_TUNE'):
+        if not self._measure or self.ldt == L.F32:
             return 0
         N, Hh, Ww, Cx = xin.shape
         key = self._key_tag + (N, Hh, Ww, Cx, c.cout, c.k, c.stride)
         if key not in self._wgrad_algo and not getattr(self.net, 'measure_live', True):
             return 0                                      # (tune='plan', a shape the plan does not hold: the library's choice)
         if key not in self._wgrad_algo:
-            cands = (0, 2, 3, 4) if (c.k == 3 and c.stride == 1) else (0, 1, 5) if c.k == 1 else (0,)
-            if self.split:
-                cands = (0, 1, 2)                     # yolo_conv_wgrad_split: the library's choice, 64 x 64, 128 x 128 tiles
+            cands = self._wgrad_algos(c)
             best, best_t = 0, float('inf')
             if len(cands) > 1:
-                lib, st = self.lib, L.stream_ptr()
+                st = L.stream_ptr()
                 # the candidates run on THIS stream with the workspace the side stream's weight gradients share (their
                 # finishing passes accumulate into it and zero it): nothing of the side stream may be in flight
                 main = torch.cuda.current_stream()
                 main.wait_stream(self._side)
                 scratch = torch.zeros((c.cout, Cx, c.k, c.k), dtype=torch.float32, device=self.dev)
-                call = lambda a: lib.yolo_conv_wgrad_algo(L.ptr(dy), L.ptr(xin.val), L.ptr(scratch), N, Hh, Ww, Cx, c.cout, c.k,
-                                                          c.stride, 0, self.ldt, L.ptr(self.wg_ws), a, st)
-                if self.split:
-                    call = lambda a: lib.yolo_conv_wgrad_split(L.ptr(dy), L.ptr(xin.val), L.ptr(scratch), N, Hh, Ww, Cx, c.cout,
-                                                               c.k, c.stride, 0, 0, self.ldt, L.ptr(self.wg_ws), a, st)
                 for a in cands:
-                    if call(a) != 0:
+                    call = self._wgrad_launch(dy, xin.val, scratch, N, Hh, Ww, Cx, c.cout, c.k, c.stride, algo=a)
+                    if call(st) != 0:
                         continue
-                    call(a)
+                    call(st)
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record()
                     for _ in range(6):
-                        call(a)
+                        call(st)
                     e1.record(); e1.synchronize()
                     t = e0.elapsed_time(e1)
                     if t < best_t * 0.98:                       # (a later candidate must win by 2 %)
@@ -602,19 +635,12 @@ class Trainer(object):
             self._wgrad_algo[key] = best
         return self._wgrad_algo[key]
 
-    def _wgrad(self, dy, names, launch, tag=''):
+    def _wgrad(self, dy, names, launch):
         """Run launch(stream) -- a weight-gradient call reading dy, which the current stream has just produced -- on the
         side stream (all of them, in order: they share one workspace).  The gradient buckets hear about `names` one
         layer later, once the current stream has been made to wait for that layer's side-stream work."""
         main = torch.cuda.current_stream()
-        flt = L.lab_knob('YOLO_SIDE_FILTER')                  # (diagnostics: exactly these classes go to the side stream)
-        side = (tag in flt.split(',')) if flt is not None else True
-        if not self._overlap or not side:
-            if self._overlap:
-                # (mixed main / side launches: earlier side-stream weight gradients use the same workspace, and a bucket
-                #  these names complete may hold gradients the side stream is still writing)
-                self._flush_wgrad()
-                main.wait_stream(self._side)
+        if not self._overlap:
             launch(main.cuda_stream)
             self.buckets.done(names)
             return
@@ -656,8 +682,6 @@ class Trainer(object):
                 t = op.get(k)
                 if t is not None:
                     t.grad, t.ready, t.ngot = None, False, 0
-            if op['kind'] == 'conv_bn':
-                op['brows'] = 0
         B = P.merged.shape[0]
         for op in reversed(P.fwd):
             kind = op['kind']
@@ -666,27 +690,18 @@ class Trainer(object):
                 hw, cpad = op['hw'], op['cpad']
                 src, src_bs, src_ps = op['src']            # this output's slice of d(loss)/d(logits), fp32
                 L.check(lib.yolo_gather_rows(src, L.ptr(op['dyp']), B, hw, c.cout, cpad, src_bs, src_ps, self.ldt, st), 'gather')
-                L.check(lib.yolo_bias_grad(L.ptr(op['dyp']), L.ptr(self.gview[c.name + '.bias']), B * hw, c.cout,
-                                           0 if self.split else cpad, self.ldt, st), 'db')
+                self._bias_grad(op['dyp'], self.gview[c.name + '.bias'], B * hw, c.cout, cpad, st)
                 N, Hh, Ww, Cx = xin.shape
-                if self.split:
-                    # (dense split rows of cpad channels: planes of round_up(cpad, 32))
-                    scp = -(-cpad // 32) * 32
-                    launch = lambda s_, c=c, op=op, xin=xin, N=N, Hh=Hh, Ww=Ww, Cx=Cx, scp=scp: L.check(
-                        lib.yolo_conv_wgrad_split(L.ptr(op['dyp']), L.ptr(xin.val), L.ptr(self.gview[c.name + '.weight']), N, Hh,
-                                                  Ww, Cx, c.cout, 1, 1, 2 * scp, scp, self.ldt, L.ptr(self.wg_ws), 0, s_), 'wgrad out')
-                else:
-                    launch = lambda s_, c=c, op=op, xin=xin, N=N, Hh=Hh, Ww=Ww, Cx=Cx, cpad=cpad: L.check(
-                        lib.yolo_conv_wgrad(L.ptr(op['dyp']), L.ptr(xin.val), L.ptr(self.gview[c.name + '.weight']),
-                                            N, Hh, Ww, Cx, c.cout, 1, 1, cpad, self.ldt, L.ptr(self.wg_ws), s_), 'wgrad out')
-                self._wgrad(op['dyp'], [c.name + '.weight', c.name + '.bias'], launch, tag='out')
+                row, lo = self._out_pitch(cpad)
+                launch = self._wgrad_launch(op['dyp'], xin.val, self.gview[c.name + '.weight'], N, Hh, Ww, Cx, c.cout, 1, 1, row, lo)
+                self._wgrad(op['dyp'], [c.name + '.weight', c.name + '.bias'], lambda s_, launch=launch: L.check(launch(s_), 'wgrad out'))
                 self._dgrad(c, op['dyp'], (N, Hh, Ww, cpad), xin, cpad)
             elif kind == 'upcat':
                 up, r, cat = op['up'], op['route'], op['cat']
                 if not up.ready:
-                    up.grad = up.gbuf if self.split else torch.empty(up.shape, dtype=self.tdt, device=self.dev)
+                    up.grad = self._grad_out(up)
                 if not r.ready:
-                    r.grad = r.gbuf if self.split else torch.empty(r.shape, dtype=self.tdt, device=self.dev)
+                    r.grad = self._grad_out(r)
                 L.check(lib.yolo_upsample2x_concat_bwd(L.ptr(cat.grad), L.ptr(up.grad), L.ptr(r.grad), r.shape[0], r.shape[1],
                                                        r.shape[2], up.shape[3], r.shape[3], int(up.ready), int(r.ready), self.ldt, st),
                         'upcat bwd')
@@ -694,77 +709,28 @@ class Trainer(object):
                 up.ngot += 1
                 r.ngot += 1
             else:
-                c, xin, y, z = op['c'], op['x'], op['yraw'], op['z']
-                dz = z.grad
-                npix = y.shape[0] * y.shape[1] * y.shape[2]
-                p = self.net.params
-                dy = op['dy'] if self.split else torch.empty(y.shape, dtype=self.tdt, device=self.dev)
-                if capture is not None and capture.get('_poison') and not self.split:
-                    dy.fill_(float('nan'))          # (diagnostics: an element the kernel does not write must show)
-                if self._bn3:
-                    L.check(lib.yolo_bn_train_bwd(L.ptr(dz), L.ptr(y.val), L.ptr(op['mean']), L.ptr(op['invstd']),
-                                                  L.ptr(p[c.name + '.gamma']), L.ptr(p[c.name + '.beta']), L.ptr(dy),
-                                                  L.ptr(self.gview[c.name + '.gamma']), L.ptr(self.gview[c.name + '.beta']),
-                                                  L.ptr(self.ws), npix, c.cout, LEAKY_SLOPE, self.ldt, st), 'bn bwd ' + c.name)
-                elif op['brows']:
-                    # the data gradient that completed dz took sum(da), sum(da * xhat) in its epilogue
-                    ws, wn = self._next_ws()
-                    L.check(lib.yolo_bn_train_bwd_partials(L.ptr(self._stats_b), op['brows'], lib.yolo_padded_channels(c.cout),
-                                                           L.ptr(dz), L.ptr(y.val), L.ptr(op['mean']), L.ptr(op['invstd']),
-                                                           L.ptr(p[c.name + '.gamma']), L.ptr(p[c.name + '.beta']), L.ptr(dy),
-                                                           L.ptr(self.gview[c.name + '.gamma']), L.ptr(self.gview[c.name + '.beta']),
-                                                           ws, wn, self.ws2[0].numel(), npix, c.cout, LEAKY_SLOPE, self.ldt, st),
-                            'bn bwd (partials) ' + c.name)
-                else:
-                    ws, wn = self._next_ws()
-                    pr = self.probe
-                    if pr is not None:                  # (measurement only, bench.py's training roofline: HIP events around the call)
-                        e0 = torch.cuda.Event(enable_timing=True)
-                        e0.record()
-                    L.check(lib.yolo_bn_train_bwd_pp(L.ptr(dz), L.ptr(y.val), L.ptr(op['mean']), L.ptr(op['invstd']),
-                                                     L.ptr(p[c.name + '.gamma']), L.ptr(p[c.name + '.beta']), L.ptr(dy),
-                                                     L.ptr(self.gview[c.name + '.gamma']), L.ptr(self.gview[c.name + '.beta']),
-                                                     ws, wn, self.ws2[0].numel(), npix, c.cout, LEAKY_SLOPE, self.ldt, st), 'bn bwd ' + c.name)
-                    if pr is not None:
-                        e1 = torch.cuda.Event(enable_timing=True)
-                        e1.record()
-                        pr.append(('bn_bwd', c.name, npix * c.cout, e0, e1))
+                c, xin, y = op['c'], op['x'], op['yraw']
+                dz = op['z'].grad
+                dy = self._dy_for(op, poison=capture is not None and capture.get('_poison'))
+                self._bn_bwd(op, dz, dy, st)
                 if capture is not None:
-                    if self.split:
-                        # the values hi + lo as fp32 (N, H, W, C) copies: the split buffers are plan-owned, and the next step
-                        # overwrites them
-                        plain = lambda t, C_=c.cout: t[..., 0, :C_].float() + t[..., 1, :C_].float()
-                        capture[c.name] = dict(dz=plain(dz), dy=plain(dy))
-                    else:
-                        capture[c.name] = dict(dz=dz.clone(), dy=dy)
+                    capture[c.name] = dict(dz=self._captured(dz, c.cout, True), dy=self._captured(dy, c.cout, False))
                 if op['res'] is not None:
                     self._accum(op['res'], dz)          # the residual branch receives dz unchanged
                 N, Hh, Ww, Cx = xin.shape
                 names = [c.name + '.weight', c.name + '.gamma', c.name + '.beta']
                 if c is g.stem:
                     def stem_wgrad(s_, c=c, dy=dy, xin=xin, N=N, Hh=Hh, Ww=Ww):
-                        # (torch ops below run on the stream _wgrad has made current)
+                        # (torch ops below run on the stream _wgrad has made current; x: the 8-channel copy of the image
+                        #  yolo_nchw_to_nhwc wrote in the forward pass)
                         dw8 = torch.zeros((c.cout, 8, 3, 3), dtype=torch.float32, device=self.dev)
-                        if self.split:
-                            # (x: the 8-channel split copy of the image yolo_nchw_to_nhwc wrote in the forward pass)
-                            L.check(lib.yolo_conv_wgrad_split(L.ptr(dy), L.ptr(xin.val), L.ptr(dw8), N, Hh, Ww, 8, c.cout, 3, 1, 0, 0,
-                                                              self.ldt, L.ptr(self.wg_ws), 0, s_), 'wgrad stem')
-                        else:
-                            L.check(lib.yolo_conv_wgrad(L.ptr(dy), L.ptr(xin.val), L.ptr(dw8), N, Hh, Ww, 8, c.cout, 3, 1, 0, self.ldt,
-                                                        L.ptr(self.wg_ws), s_), 'wgrad stem')
+                        L.check(self._wgrad_launch(dy, xin.val, dw8, N, Hh, Ww, 8, c.cout, 3, 1)(s_), 'wgrad stem')
                         self.gview[c.name + '.weight'].copy_(dw8[:, :3])
-                    self._wgrad(dy, names, stem_wgrad, tag='stem')
+                    self._wgrad(dy, names, stem_wgrad)
                 else:
-                    wa = self._wgrad_algo_for(c, dy, xin)
-                    if self.split:
-                        launch = lambda s_, c=c, dy=dy, xin=xin, N=N, Hh=Hh, Ww=Ww, Cx=Cx, wa=wa: L.check(
-                            lib.yolo_conv_wgrad_split(L.ptr(dy), L.ptr(xin.val), L.ptr(self.gview[c.name + '.weight']), N, Hh, Ww,
-                                                      Cx, c.cout, c.k, c.stride, 0, 0, self.ldt, L.ptr(self.wg_ws), wa, s_), 'wgrad ' + c.name)
-                    else:
-                        launch = lambda s_, c=c, dy=dy, xin=xin, N=N, Hh=Hh, Ww=Ww, Cx=Cx, wa=wa: L.check(
-                            lib.yolo_conv_wgrad_algo(L.ptr(dy), L.ptr(xin.val), L.ptr(self.gview[c.name + '.weight']), N, Hh, Ww,
-                                                     Cx, c.cout, c.k, c.stride, 0, self.ldt, L.ptr(self.wg_ws), wa, s_), 'wgrad ' + c.name)
-                    self._wgrad(dy, names, launch, tag=self._wgrad_tag(c, Cx))
+                    launch = self._wgrad_launch(dy, xin.val, self.gview[c.name + '.weight'], N, Hh, Ww, Cx, c.cout, c.k, c.stride,
+                                                algo=self._wgrad_algo_for(c, dy, xin))
+                    self._wgrad(dy, names, lambda s_, launch=launch, c=c: L.check(launch(s_), 'wgrad ' + c.name))
                     self._dgrad(c, dy, y.shape, xin, c.cout)
         self._flush_wgrad()
         if self._overlap:
