@@ -122,7 +122,7 @@ def get_loss(x, y, s_weight, mask, scale=DEFAULT_SCALE, car_rotate=False):
 
 
 def loss_and_grad_wrt_output(merged_out, labels, spec, size, scale=DEFAULT_SCALE,
-                             positive_weight=1.0, negative_weight=0.1):
+                             positive_weight=1.0, negative_weight=0.1, car_rotate=False):
     """Loss vectors and d(sum of all losses)/d(net output) for a merged (B,N,A,C) fp32 output."""
     steps = detect.init_steps(spec['layers'], spec['all_anchors'])
     area = detect.init_area(size, steps)
@@ -135,7 +135,7 @@ def loss_and_grad_wrt_output(merged_out, labels, spec, size, scale=DEFAULT_SCALE
     xs, i = [], 0
     for pt in sp:
         xs.append(out[..., i:pt]); i = pt
-    losses = get_loss(xs, y, sw, mask, scale)
+    losses = get_loss(xs, y, sw, mask, scale, car_rotate)
     total = sum(l.sum() for l in losses)      # sum(losses).backward() on (B,) vectors = sum over batch
     total.backward()
     return [l.detach().numpy() for l in losses], out.grad.numpy(), (y, mask, sw)
@@ -187,9 +187,11 @@ def synthetic_labels(batch, seed=3, render_rate=0.5, num_class=24):
     return lab
 
 
-def train_step_reference(g, P, x, labels, spec, size, scale=DEFAULT_SCALE, sim_bf16=False):
+def train_step_reference(g, P, x, labels, spec, size, scale=DEFAULT_SCALE, sim_bf16=False, car_rotate=False,
+                         positive_weight=1.0, negative_weight=0.1):
     """One forward (train-mode BN) + loss + backward on the torch-CPU graph; returns losses and
-    gradients w.r.t. every trainable parameter (dict name -> ndarray)."""
+    gradients w.r.t. every trainable parameter (dict name -> ndarray).  car_rotate / positive_weight / negative_weight:
+    _train_batch's own switches (car/YOLO.py:350, 482-496)."""
     Pt = {}
     for k, v in P.items():
         t = torch.from_numpy(np.ascontiguousarray(v)).clone()
@@ -204,11 +206,11 @@ def train_step_reference(g, P, x, labels, spec, size, scale=DEFAULT_SCALE, sim_b
     anchors_ltrb = detect.get_default_ltrb(size, steps, spec['all_anchors'])
     sp = spec['slice_point']
     y, mask = loss_mask(labels, anchors_ltrb, spec['all_anchors'], size, steps, area, sp[-1] - sp[-2])
-    sw = score_weight(mask)
+    sw = score_weight(mask, positive_weight, negative_weight)
     xs, i = [], 0
     for pt in sp:
         xs.append(merged[..., i:pt]); i = pt
-    losses = get_loss(xs, y, sw, mask, scale)
+    losses = get_loss(xs, y, sw, mask, scale, car_rotate)
     sum(l.sum() for l in losses).backward()
     grads = {k: t.grad.numpy() for k, t in Pt.items() if t.requires_grad and t.grad is not None}
     return [l.detach().numpy() for l in losses], grads, merged.detach().numpy()

@@ -71,6 +71,43 @@ def test_train_step_losses_and_grads(cuda):
     assert np.mean([v < 1e-2 for v in rel.values()]) > 0.8
 
 
+def test_train_step_with_rotation_loss_and_score_weights(cuda):
+    """_train_batch(..., car_rotate=True) (car/YOLO.py:350, 491-496) with a non-zero rotation scale and score weights that are not
+    the defaults: the third Huber group end to end, against the oracle switched the same way."""
+    from yolo_amd.net import CarNet
+    from yolo_amd.train import Trainer
+    spec, size = og.spec_micro(), (64, 96)
+    g = og.build_graph(spec)
+    P = og.init_params(g, seed=0, bn='random')
+    x = np.random.default_rng(2).random((2, 3) + size, dtype=np.float32)
+    lab = ot.synthetic_labels(2, seed=1, render_rate=0.0, num_class=4)
+    assert (lab[:, 0, 0] >= 0).all() and (lab[:, 0, 5] != 0).all()           # every image has an object with a non-zero rotation
+    scale = dict(ot.DEFAULT_SCALE, rotate=0.5)
+    kw = dict(scale=scale, car_rotate=True, positive_weight=2.0, negative_weight=0.2)
+    net = CarNet(spec, dtype='f32', device=cuda).load_params(P)
+    tr = Trainer(net, size, **kw)
+    losses = tr.train_step(torch.from_numpy(x).to(cuda), torch.from_numpy(lab).to(cuda), update=False).cpu().numpy()
+    rl, rg, rmerged = ot.train_step_reference(g, P, x, lab, spec, size, **kw)
+    np.testing.assert_allclose(losses, np.stack(rl), rtol=1e-3, atol=1e-7)
+    assert (losses[3] != 0).all() and (np.stack(rl)[3] != 0).all()
+    grads = tr.grads()
+    assert set(grads) == set(rg)
+    rel = {}
+    for name in sorted(rg):                                                  # the three L2 conditions of test_train_step_losses_and_grads
+        a, b = grads[name].cpu().numpy().astype(np.float64), rg[name].astype(np.float64)
+        rel[name] = np.linalg.norm(a - b) / (np.linalg.norm(b) + 1e-30)
+    worst = max(rel, key=rel.get)
+    assert rel[worst] < 0.1, (worst, rel[worst])
+    assert np.median(list(rel.values())) < 2e-3, np.median(list(rel.values()))
+    assert np.mean([v < 1e-2 for v in rel.values()]) > 0.8
+    # the rotation channel of d(losses)/d(logits), at the step's own logits (no forward difference in the way)
+    merged = tr.merged_logits().cpu().numpy()
+    _, gout, _ = ot.loss_and_grad_wrt_output(merged, lab, spec, size, scale, 2.0, 0.2, car_rotate=True)
+    dm = tr._last[0].dmerged.cpu().numpy().reshape(gout.shape)
+    top = np.abs(gout[..., 5]).max()
+    assert top > 0 and np.abs(dm[..., 5] - gout[..., 5]).max() <= 1e-4 * top
+
+
 def test_loss_grad_wrt_logits(cuda):
     """d(sum of losses)/d(logits) alone, on random logits (isolates loss.hip from the network)."""
     from yolo_amd import lib as L

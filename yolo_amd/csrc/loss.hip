@@ -39,12 +39,16 @@ __global__ __launch_bounds__(256) void assign_kernel(const float* __restrict__ l
         return;
     }
     const float Ly = L[1], Lx = L[2], Lh = L[3], Lw = L[4];
+    // A NaN in any coordinate makes every IoU of the reference NaN (its maximum / minimum propagate NaN; fmaxf / fminf drop it and
+    // would leave finite IoUs for a NaN centre): no box is compared, and box 0 is taken below.
+    const bool nan_label = Ly != Ly || Lx != Lx || Lh != Lh || Lw != Lw;
     float bv = -FLT_MAX;
     int bi = 0x7fffffff;
-    for (int k = threadIdx.x; k < g.nbox; k += blockDim.x) {
-        const float v = iou_ltrb_yxhw(anchors_ltrb[k], Ly, Lx, Lh, Lw);
-        if (v > bv) { bv = v; bi = k; }
-    }
+    if (!nan_label)
+        for (int k = threadIdx.x; k < g.nbox; k += blockDim.x) {
+            const float v = iou_ltrb_yxhw(anchors_ltrb[k], Ly, Lx, Lh, Lw);
+            if (v > bv) { bv = v; bi = k; }
+        }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         const float ov = __shfl_xor(bv, off, 64);
@@ -67,9 +71,9 @@ __global__ __launch_bounds__(256) void assign_kernel(const float* __restrict__ l
         const float4 b = anchors_ltrb[k];
         const float step = (float)g.step[layer];
         float sty = (Ly - (b.w + b.y) / 2.f) * (float)g.img_h / step + 0.5f;
-        sty = fminf(fmaxf(sty, 0.0001f), 0.9999f);
+        sty = sty != sty ? sty : fminf(fmaxf(sty, 0.0001f), 0.9999f);      // (clip keeps a NaN, as the reference's)
         float stx = (Lx - (b.z + b.x) / 2.f) * (float)g.img_w / step + 0.5f;
-        stx = fminf(fmaxf(stx, 0.0001f), 0.9999f);
+        stx = stx != stx ? stx : fminf(fmaxf(stx, 0.0001f), 0.9999f);
         R[0] = 1.f;
         R[1] = (float)k;
         R[2] = -logf(1.f / sty - 1.f);
@@ -165,7 +169,7 @@ __global__ __launch_bounds__(256) void loss_kernel(const float* __restrict__ log
                 const int grp = j < cfg.g1 ? 0 : (j < cfg.g1 + cfg.g2 ? 1 : 2);
                 const float w = grp == 0 ? w1 : (grp == 1 ? w2 : w3);
                 if (grp == 0) l_1 += l * w; else if (grp == 1) l_2 += l * w; else l_3 += l * w;
-                d[1 + j] = gr * w;
+                d[1 + j] = R ? gr * w : 0.f;           // (a background box: +0, not the -0 of a negative gradient times w = 0)
             }
         }
         // class: soft-label softmax cross-entropy, weight = mask * scale, mean over (N,A,1)
