@@ -266,6 +266,57 @@ int yolo_render_stats(const unsigned char* atlas, long long atlas_bytes, const v
 int yolo_render_cars(const float* bg, const unsigned char* atlas, long long atlas_bytes, const void* rows, const void* workspace,
                      float* out, int N, int H, int W, void* stream);
 
+/* LPGenerator.add (yolo_modules/licence_plate_render/__init__.py:58-166) with the PIXELS made on the device, the plate counterpart
+ * of yolo_render_cars: the host decides (glyphs, 6-D pose, blur, noise key, colour: yolo_amd/render.py LPGenerator.draw_params) and
+ * hands over one row of YOLO_PLATE_ROW_WORDS 32-bit words per image:
+ *   0 has-plate (int)      1..7 glyph ids (int; 3 letters 10..33, then 4 digits 0..9)      8..11 window l, t, r, b (int; r, b exclusive)
+ *   12,13 noise key k0, k1 (uint32)     14 noise scale s (float; 0 = no noise)     15 unused
+ *   16..24 m0..m8 (float): output pixel INDEX -> plate texel INDEX, projective     25 w0  26 w1 (float)
+ *   27..35 A  36..44 D (3x3 row-major, float)   45..47 e (float)
+ * glyphs: the resident uint8 RGBA atlas in a fixed layout, YOLO_PLATE_GLYPH_BYTES in all, 4-byte aligned: the 34 glyphs as (90,45,4)
+ * in id order 0..33, then the dot as (70,10,4) -- the images LPGenerator holds after its PIL resize.  rows ON THE DEVICE, 8-byte
+ * aligned; plates (N,160,380,4) uint8, caller-owned, 4-byte aligned; bg (N,3,H,W) f32 ALREADY 0..1, out the same shape, dense.
+ *  yolo_plate_compose: every texel of an image's plate starts as (255,255,255,255); a glyph cell overwrites all four bytes (PIL's
+ *   mask-less paste): glyph k of 7 at column (7, 56, 106, 175, 225, 274, 324)[k], row 35, 45 wide, 90 high; the dot at column 158,
+ *   row 45, 10 wide, 70 high (the cells do not overlap).  A row with has == 0 or any glyph id outside 0..33 is "no plate": its
+ *   plate is NOT written, and the two other entries treat the image as background only.  No load leaves the atlas whatever a row holds.
+ * The arithmetic of the pixels, every operation in fp32, in this order, nothing fused, division correctly rounded (this is the
+ * definition; tests/plate_ref.py restates it).  For output position (column x, row y):
+ *   nx = (m0*x + m1*y) + m2;  ny = (m3*x + m4*y) + m5;  den = (m6*x + m7*y) + m8
+ *   !(den > 0) or den not finite:  S = 0 (transparent);   otherwise sx = nx / den, sy = ny / den and S is yolo_render_cars' bilinear
+ *   tap over the image's plate at (sx, sy): x0 = floor(sx), fx = sx - x0, ..., taps outside read 0, indices limited to +-2^30,
+ *   addresses clamped into the plate.
+ *  P(j, i): inside the window S(j, i), or for w1 != 0 the 3x3 separable sum in yolo_render_cars' order; outside the window P = 0 and
+ *   nothing is sampled.
+ *  Q(j, i), four channels, for EVERY canvas pixel:  s == 0: Q = P.  Otherwise two Philox4x32-10 calls with key (k0, k1), call h of
+ *   0, 1 with counter (j, i, h, 0); call 0 gives words 0,1 for R and 2,3 for G, call 1 gives B and A the same way; per channel
+ *   t = the sum of the 8 bytes of its two words, z = (float)(t - 1020), Q_c = min(max(P_c + z*s, 0), 255).  Integer-only on
+ *   purpose: an 8-term Irwin-Hall sum, exactly reproducible (Box-Muller's logf / cosf would not be); the host sets
+ *   s = float32(sigma / sqrt(8 * 65535 / 12)), which gives z*s the standard deviation sigma.
+ *   The noise falls on ALL FOUR channels of the WHOLE canvas, as the reference's np.clip(px + normal(0, 5)) on the RGBA array does
+ *   (alpha outside the plate becomes a faint haze).  Nothing is quantised to integer levels: PIL quantises at every stage, this is
+ *   a float pipeline like the cars'.
+ *  yolo_plate_stats: per image and channel c of R, G, B the sum of Q_c over ALL canvas pixels (pixels whose Q is known to be 0 --
+ *   s == 0 and outside the window -- are passed over), each converted to double and added in double, as 16 partial sums whose
+ *   order does not depend on the window (workspace: yolo_plate_workspace_bytes(N, H, W) bytes, 8-byte aligned, caller-owned); no
+ *   atomics.
+ *  yolo_plate_render: mu_c, k_c as yolo_render_cars computes them from the partials, D and e;  per pixel
+ *   fg_c = (((A[c][0]*Q_0 + A[c][1]*Q_1) + A[c][2]*Q_2) + k_c) / 255.f;   mask = Q_3 / 255.f
+ *   out_c = min(max(bg_c * (1.f - mask) + fg_c * mask, 0), 1)                     (yolo_composite_unit's operation order)
+ *  With s == 0 a pixel outside the window, and every pixel of a no-plate image whatever s is: out_c = min(max(bg_c, 0), 1).
+ *  out may alias bg: each thread reads its pixels before it writes them.
+ * YOLO_EINVAL: a NULL pointer, a non-positive N, H or W, a misaligned pointer.  YOLO_EUNSUPPORTED: H * ceil(W / 4) beyond 2^31.
+ * Validation comes before any launch.  yolo_plate_workspace_bytes returns YOLO_EINVAL for a non-positive size.
+ * 16-byte bg loads and plane stores when W % 4 == 0 and bg, out are 16-byte aligned, scalar ones otherwise.
+ * Stream order: yolo_plate_compose, yolo_plate_stats, yolo_plate_render on the same rows. */
+#define YOLO_PLATE_ROW_WORDS 48
+#define YOLO_PLATE_GLYPH_BYTES 553600
+long long yolo_plate_workspace_bytes(int N, int H, int W);
+int yolo_plate_compose(const unsigned char* glyphs, const void* rows, unsigned char* plates, int N, void* stream);
+int yolo_plate_stats(const unsigned char* plates, const void* rows, void* workspace, int N, int H, int W, void* stream);
+int yolo_plate_render(const float* bg, const unsigned char* plates, const void* rows, const void* workspace, float* out, int N, int H,
+                      int W, void* stream);
+
 /* 2x nearest up-sample of `up` (N,H/2,W/2,C1) + channel concat with `route` (N,H,W,C2) ->
  * (N,H,W,C1+C2), up-sampled channels first: gluoncv _upsample + F.concat, car/utils.py:92-93. */
 int yolo_upsample2x_concat(const void* up, const void* route, void* y, int N, int H, int W,

@@ -17,7 +17,7 @@ def __getattr__(name):
     if name in ('FrameIntake', 'intake_matrix', 'warp_u8', 'rectify_plates'):
         from . import intake
         return getattr(intake, name)
-    if name in ('RenderCar', 'SpriteAtlas'):
+    if name in ('RenderCar', 'SpriteAtlas', 'LPGenerator', 'PlateCamera'):
         from . import render
         return getattr(render, name)
     raise AttributeError(name)

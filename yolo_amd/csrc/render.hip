@@ -9,10 +9,10 @@
 // the three planes (16-byte loads and stores when W % 4 == 0 and bg / out are 16-byte aligned, scalar ones with a tail thread
 // otherwise).  The row of an image is read at a block-uniform address, so it arrives through scalar loads.
 #include "common.h"
+#include "render_sample.h"
 
 constexpr int RENDER_THREADS = 256;
 constexpr int RENDER_STAT_BLOCKS = 16;                    // partial sums per image (the workspace holds 3 doubles for each)
-constexpr float RENDER_IDX_LIMIT = 1073741824.f;          // 2^30: tap indices are clamped here before the int conversion
 
 struct RenderRow {                                        // YOLO_RENDER_ROW_WORDS 32-bit words (include/yolo_amd.h)
     int has, h, w;
@@ -47,60 +47,17 @@ __device__ __forceinline__ RenderLevel render_level(const RenderRow& R, const un
     return v;
 }
 
-// The four channels of the sample at output position (x, y): bilinear over 4-byte RGBA pixels, one 32-bit load per tap.  Every
-// tap ADDRESS is clamped into the level, so no load leaves it whatever the affine holds; a tap whose index was outside reads 0.
+// The four channels of the sample at output position (x, y): the bilinear tap (render_sample.h) at the affine's image of it.
 __device__ __forceinline__ void render_sample(const unsigned char* __restrict__ level, int h, int w, const float* a, float x, float y,
                                               float* val) {
     const float sx = (a[0] * x + a[1] * y) + a[2];
     const float sy = (a[3] * x + a[4] * y) + a[5];
-    const float x0f = floorf(sx), y0f = floorf(sy);
-    const float fx = sx - x0f, fy = sy - y0f;
-    // (fmaxf / fminf return the other operand for a NaN: a NaN coordinate indexes far outside, and the value is NaN through fx)
-    const int x0 = (int)fminf(fmaxf(x0f, -RENDER_IDX_LIMIT), RENDER_IDX_LIMIT), x1 = x0 + 1;
-    const int y0 = (int)fminf(fmaxf(y0f, -RENDER_IDX_LIMIT), RENDER_IDX_LIMIT), y1 = y0 + 1;
-    const int cx0 = min(max(x0, 0), w - 1), cx1 = min(max(x1, 0), w - 1);
-    const int cy0 = min(max(y0, 0), h - 1), cy1 = min(max(y1, 0), h - 1);
-    const bool inx0 = cx0 == x0, inx1 = cx1 == x1, iny0 = cy0 == y0, iny1 = cy1 == y1;
-    const uint32_t* px = reinterpret_cast<const uint32_t*>(level);
-    const long long r0 = (long long)cy0 * w, r1 = (long long)cy1 * w;
-    const uint32_t pa = (inx0 && iny0) ? px[r0 + cx0] : 0u;
-    const uint32_t pb = (inx1 && iny0) ? px[r0 + cx1] : 0u;
-    const uint32_t pc = (inx0 && iny1) ? px[r1 + cx0] : 0u;
-    const uint32_t pd = (inx1 && iny1) ? px[r1 + cx1] : 0u;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const float ta = (float)((pa >> (8 * c)) & 255u), tb = (float)((pb >> (8 * c)) & 255u);
-        const float tc = (float)((pc >> (8 * c)) & 255u), td = (float)((pd >> (8 * c)) & 255u);
-        const float top = ta + fx * (tb - ta);
-        const float bot = tc + fx * (td - tc);
-        val[c] = top + fy * (bot - top);
-    }
+    render_tap(level, h, w, sx, sy, val);
 }
 
-// RGBA 0..255 of output pixels (j0..j0+3, i) before the colour map.  w1 == 0 (uniform per image): the sample itself.  Otherwise
-// the separable 3x3 sum in a fixed order: rows i-1, i, i+1 each as (w1 S(j-1) + w0 S(j)) + w1 S(j+1), then the same over the rows.
-// The six columns j0-1..j0+4 of a row are sampled once and shared by the four pixels (the same values, so the same bits).
+// RGBA 0..255 of output pixels (j0..j0+3, i) before the colour map: the sample, or its 3x3 separable blur (render_sample.h)
 __device__ __forceinline__ void render_quad(const RenderLevel& v, const float* a, float w0, float w1, int j0, int i, float (*px)[4]) {
-    if (w1 == 0.f) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) render_sample(v.level, v.h, v.w, a, (float)(j0 + e), (float)i, px[e]);
-        return;
-    }
-    // (one row at a time, not unrolled: the three rows' 72 taps in flight at once cost ~170 VGPRs and half the resident waves)
-#pragma unroll 1
-    for (int dy = 0; dy < 3; ++dy) {
-        float s[6][4];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) render_sample(v.level, v.h, v.w, a, (float)(j0 - 1 + k), (float)(i - 1 + dy), s[k]);
-        const float wy = dy == 1 ? w0 : w1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float row = (w1 * s[e][c] + w0 * s[e + 1][c]) + w1 * s[e + 2][c];
-                px[e][c] = dy == 0 ? wy * row : px[e][c] + wy * row;
-            }
-    }
+    render_blur_quad([&](float x, float y, float* val) { render_sample(v.level, v.h, v.w, a, x, y, val); }, w0, w1, j0, i, px);
 }
 
 // grid (RENDER_STAT_BLOCKS, images).  The threads of an image walk the column groups of its WINDOW only (rows t..b-1, groups
@@ -160,17 +117,7 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_cars_kernel(const float
     const long long plane = (long long)H * W;
     const long long base = n * 3 * plane + (long long)i * W + j0;           // 64-bit: B 3 H W passes 2^31 from 1380 images of 416^2 on
     float b[3][4];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        if constexpr (VEC) {
-            const f32x4 t = *reinterpret_cast<const f32x4*>(bg + base + c * plane);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) b[c][e] = t[e];
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) b[c][e] = (j0 + e < W) ? bg[base + c * plane + e] : 0.f;
-        }
-    }
+    render_load_planes<VEC>(bg, base, plane, j0, W, b);
     const RenderRow& R = rows[n];
     const RenderLevel v = render_level(R, atlas, atlas_bytes, H, W);
     float o[3][4];
@@ -210,17 +157,7 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_cars_kernel(const float
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[c][e] = fminf(fmaxf(b[c][e] / 255.f, 0.f), 1.f);
     }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        if constexpr (VEC) {
-            const f32x4 t = {o[c][0], o[c][1], o[c][2], o[c][3]};
-            *reinterpret_cast<f32x4*>(out + base + c * plane) = t;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (j0 + e < W) out[base + c * plane + e] = o[c][e];
-        }
-    }
+    render_store_planes<VEC>(out, base, plane, j0, W, o);
 }
 
 static int render_check(const void* atlas, long long atlas_bytes, const void* rows, int N, int H, int W) {

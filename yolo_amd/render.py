@@ -9,6 +9,7 @@ are training data that is not part of the reference repository: RenderCar takes 
 
 RenderCar.render_device makes the same batch with the PIXELS drawn on the device too (csrc/render.hip): the host only makes the
 draws (draw_params: one row of scalars per image), a resident uint8 RGBA SpriteAtlas holds the sprites and their mip levels.
+LPGenerator.add_device does the same for the licence plates (csrc/plates.hip), from a resident glyph atlas.
 """
 import math
 import os
@@ -611,6 +612,13 @@ class RenderCar(object):
 # ---- LPGenerator.add (yolo_modules/licence_plate_render/__init__.py:21-166, 273-371): licence plates for CarLPNet ---------
 LP_CORNERS = np.float32([[380, 160], [0, 160], [0, 0], [380, 0]])       # (:118: the plate image's corners, as projected)
 LP_GLYPH_X = (7, 56, 106, 158, 175, 225, 274, 324)                      # (:28: glyph columns of the 'ABC-1234' plate)
+# the device route (csrc/plates.hip; include/yolo_amd.h, yolo_plate_render): one row of PLATE_ROW_WORDS 32-bit words per image
+#   0 has-plate   1..7 glyph ids   8..11 window l, t, r, b   12,13 noise key   14 noise scale   16..24 the projective map m0..m8
+#   25 w0   26 w1   27..35 A   36..44 D   45..47 e                                                         (15: padding)
+PLATE_ROW_WORDS = 48
+PLATE_GLYPH_BYTES = 34 * 90 * 45 * 4 + 70 * 10 * 4
+# the noise is sigma times an 8-term Irwin-Hall sum of bytes: its standard deviation before scaling (a byte's variance is 65535/12)
+PLATE_NOISE_UNIT = math.sqrt(8 * 65535 / 12.0)
 
 
 def homography(src, dst):
@@ -721,6 +729,130 @@ class LPGenerator(object):
             mask[i], fg[i], labels[i, 0, :9] = self.random_projection_LP_6D(plate, (h, w), r_max)
             labels[i, 0, 9] = lp_type
         return fg, mask, labels
+
+    # ---- the same plates drawn on the device (csrc/plates.hip): decisions here, pixels there ----------------------------------
+    def glyph_atlas(self):
+        """The glyph images as the device holds them: uint8 RGBA bytes, the 34 glyphs as (90,45,4) in id order, then the dot
+        as (70,10,4) -- PLATE_GLYPH_BYTES in all (include/yolo_amd.h, yolo_plate_compose).  Built once."""
+        if getattr(self, '_glyph_atlas', None) is None:
+            parts = [np.asarray(g if g.mode == 'RGBA' else g.convert('RGBA'), np.uint8).reshape(-1) for g in self.glyph + [self.dot]]
+            data = np.ascontiguousarray(np.concatenate(parts))
+            if data.size != PLATE_GLYPH_BYTES:
+                raise ValueError('the glyph atlas has %d bytes, not %d' % (data.size, PLATE_GLYPH_BYTES))
+            self._glyph_atlas = data
+        return self._glyph_atlas
+
+    def plate_row(self, ids, pose, h, w, sigma_blur, key, sigma_noise=5.0, color=None):
+        """One parameter row (PLATE_ROW_WORDS int32 words, floats stored by bit pattern) of a plate with the 7 glyph `ids`
+        at `pose` [X, Y, Z, r1, r2, r3] on an (h, w) canvas; key = (k0, k1); color = (A, D, e) or None for the identity.
+        The map takes a canvas pixel INDEX to a plate texel INDEX: index -> continuous (+0.5) -> camera pixel (the canvas is the
+        camera image resized) -> the plate through homography(corners(pose), LP_CORNERS) -> index (-0.5); composed in
+        float64, stored as float32, not normalised."""
+        cam = self.camera
+        half = np.array([[1.0, 0.0, 0.5], [0.0, 1.0, 0.5], [0.0, 0.0, 1.0]])
+        to_cam = np.diag([cam.w / float(w), cam.h / float(h), 1.0])
+        M = np.linalg.inv(half) @ homography(cam.corners(pose), LP_CORNERS) @ to_cam @ half
+        # the window: a sample is non-zero only for texel indices in (-1, 380) x (-1, 160); that rectangle carried to the canvas
+        F = np.linalg.inv(M)
+        tx, ty = np.float64([-1, 380, 380, -1]), np.float64([-1, -1, 160, 160])
+        den = F[2, 0] * tx + F[2, 1] * ty + F[2, 2]
+        if (den * den[0] <= 0).any():                             # (the rectangle crosses the map's horizon: no bound to take)
+            win = [0, 0, w, h]
+        else:
+            px, py = (F[0, 0] * tx + F[0, 1] * ty + F[0, 2]) / den, (F[1, 0] * tx + F[1, 1] * ty + F[1, 2]) / den
+            slack = 1.01                                          # 1 px for the blur, 0.01 for the float32 matrix
+            win = [int(math.floor(px.min() - slack)), int(math.floor(py.min() - slack)),
+                   int(math.ceil(px.max() + slack)) + 1, int(math.ceil(py.max() + slack)) + 1]
+            win = [min(max(win[0], 0), w), min(max(win[1], 0), h), min(max(win[2], 0), w), min(max(win[3], 0), h)]
+        row = np.zeros(PLATE_ROW_WORDS, np.int32)
+        fl = row.view(np.float32)
+        row[0] = 1
+        row[1:8] = ids
+        row[8:12] = win
+        row[12:14] = np.asarray(key, np.uint32).view(np.int32)
+        fl[14] = np.float32(sigma_noise / PLATE_NOISE_UNIT)
+        fl[16:25] = M.reshape(-1).astype(np.float32)
+        fl[25:27] = np.float64(blur_weights(sigma_blur)).astype(np.float32)
+        A, D, e = (np.eye(3), np.zeros((3, 3)), np.zeros(3)) if color is None else color
+        fl[27:36], fl[36:45], fl[45:48] = (np.asarray(A, np.float64).reshape(-1).astype(np.float32),
+                                           np.asarray(D, np.float64).reshape(-1).astype(np.float32), np.asarray(e, np.float64).astype(np.float32))
+        return row
+
+    def draw_params(self, batch, h, w, r_max, add_rate=1.0):
+        """add_host's draws, in its order and from the same np.random / random streams, without touching a pixel:
+        -> (labels (B,1,10) float32, rows (B, PLATE_ROW_WORDS) int32).  Host only: needs neither torch nor a GPU.
+        Per image: the add-rate draw, three letters, four digits (4 -> 9), Z, X, Y, three angles, the blur radius; then TWO
+        uint32 key words (np.random.randint) where the host route draws h*w*4 normals; then the colour augmenter's draws.
+        So the first plate of a batch has add_host's glyphs, pose and label; after it the two routes' streams have parted."""
+        labels = -np.ones((batch, 1, 10), np.float32)
+        rows = np.zeros((batch, PLATE_ROW_WORDS), np.int32)
+        for i in range(batch):
+            if np.random.rand() > add_rate:
+                continue
+            ids = [int(g) for g in np.random.randint(10, 34, size=3)]
+            ids += [9 if g == 4 else int(g) for g in np.random.randint(0, 9, size=4)]
+            Z = np.random.uniform(low=1500., high=5000.)
+            X = (Z * 9 / 30.) * np.random.uniform(low=-1, high=1)
+            Y = (Z * 7 / 30.) * np.random.uniform(low=-1, high=1)
+            rot = [np.random.uniform(low=-1, high=1) * r_max[k] * math.pi / 180. for k in range(3)]
+            sigma = np.random.rand() * 1.0
+            key = np.random.randint(0, 2 ** 32, size=2, dtype=np.uint32)
+            color = self.augs.affine() if self.augs is not None else None
+            rows[i] = self.plate_row(ids, [X, Y, Z] + rot, h, w, sigma, key, 5.0, color)
+            x, y = self.camera.centre(X, Y, Z, h, w)
+            labels[i, 0] = np.asarray([1, X, Y, Z, rot[0], rot[1], rot[2], x, y, 0], np.float32)
+        return labels, rows
+
+    def add_device(self, imgs, r_max, add_rate=1.0, out=None):
+        """add() with the pixels made on the device: imgs (B,3,h,w) float32 0..1 CUDA tensor (RenderCar.render_device's output)
+        -> (images with plates, labels (B,1,10)), both on the device.  The host draws the parameter rows (draw_params); rows and
+        labels go up in ONE pinned, non-blocking copy; yolo_plate_compose writes the plates from the resident glyph atlas,
+        yolo_plate_stats takes each canvas's mean colour, yolo_plate_render samples, blurs, noises, colours and blends.  Runs on
+        the current stream and does not synchronise.  out=imgs draws in place."""
+        import torch
+        from . import lib as L
+        lib = L.load()
+        if imgs.dim() != 4 or imgs.shape[1] != 3 or imgs.dtype != torch.float32 or not imgs.is_cuda:
+            raise ValueError('imgs should be a float32 CUDA tensor of shape (B, 3, h, w)')
+        B, _, h, w = imgs.shape
+        dev = imgs.device
+        L.require_current_device(dev, 'this add_device call')
+        imgs = imgs.contiguous()
+        if out is None:
+            out = torch.empty_like(imgs)
+        elif tuple(out.shape) != tuple(imgs.shape) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+            raise ValueError('out should be a contiguous float32 tensor of shape %r on %s' % (tuple(imgs.shape), dev))
+        labels, rows = self.draw_params(B, h, w, r_max, add_rate)
+        state = self.__dict__.setdefault('_device_state', {})
+        if state.get('device') != dev:
+            state.clear()
+            state.update(device=dev, atlas=torch.from_numpy(self.glyph_atlas()).to(dev), stage={}, plates={}, work={})
+        nrow, nlab = rows.size * 4, labels.size * 4
+        slot = state['stage'].get(B)
+        if slot is None:
+            slot = state['stage'][B] = [torch.empty(nrow + nlab, dtype=torch.uint8, pin_memory=True), torch.cuda.Event()]
+        else:
+            slot[1].synchronize()         # the previous upload has left the staging buffer (waits for that copy only)
+        host = slot[0].numpy()
+        host[:nrow] = rows.reshape(-1).view(np.uint8)
+        host[nrow:] = labels.reshape(-1).view(np.uint8)
+        up = torch.empty(nrow + nlab, dtype=torch.uint8, device=dev)
+        up.copy_(slot[0], non_blocking=True)
+        slot[1].record()
+        plates = state['plates'].get(B)
+        if plates is None:
+            plates = state['plates'][B] = torch.empty((B, 160, 380, 4), dtype=torch.uint8, device=dev)
+        work = state['work'].get((B, h, w))
+        if work is None:
+            nbytes = lib.yolo_plate_workspace_bytes(B, h, w)
+            if nbytes <= 0:
+                raise L.YoloError('plate_workspace_bytes failed with status %d' % nbytes)
+            work = state['work'][(B, h, w)] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        st = L.stream_ptr()
+        L.check(lib.yolo_plate_compose(L.ptr(state['atlas']), L.ptr(up), L.ptr(plates), B, st), 'plate_compose')
+        L.check(lib.yolo_plate_stats(L.ptr(plates), L.ptr(up), L.ptr(work), B, h, w, st), 'plate_stats')
+        L.check(lib.yolo_plate_render(L.ptr(imgs), L.ptr(plates), L.ptr(up), L.ptr(work), L.ptr(out), B, h, w, st), 'plate_render')
+        return out, up[nrow:].view(torch.float32).view(B, 1, 10)
 
     def add(self, bg_batch, r_max, add_rate=1.0):
         """(:134-166) bg_batch (B,3,h,w) float32 0..1 CUDA tensor (RenderCar.render's output) -> (images with plates, labels)."""
