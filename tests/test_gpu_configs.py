@@ -521,4 +521,5 @@ def test_tune_plan_is_the_benched_and_tested_kernel_set(cuda):
     for o, r in zip(outs, ref):
         assert float((o - r).abs().max()) <= 0.05 * float(r.abs().max())
     tr = Trainer(CarNet(spec, dtype='bf16', device=cuda, tune='plan').load_params(P), SIZE)
-    assert len(tr._wgrad_algo) == len(state['wgrad']) and len(tr._dgrad_algo) == len(state['dgrad'])
+    held = tr.tuning_state()
+    assert len(held['wgrad']) == len(state['wgrad']) and len(held['dgrad']) == len(state['dgrad'])

@@ -448,9 +448,10 @@ def test_trainer_ignores_the_plans_bf16_gradient_choices(cuda, dtype):
     *_, tr16 = _setup(cuda, dtype='bf16', tune='measure')
     state = tr16.tune(xt, lt)
     assert state['dgrad'] and state['wgrad']
-    net._plan_state = dict(net._plan_state, dgrad={k: 99 for k in state['dgrad']}, wgrad={k: 99 for k in state['wgrad']})
+    tr.load_tuning_state({'algo': {}, 'dgrad': {k: 99 for k in state['dgrad']}, 'wgrad': {k: 99 for k in state['wgrad']}})
     tr = Trainer(net, size)
-    assert set(state['dgrad']) <= set(tr._dgrad_algo)                     # the foreign entries are there ...
+    held = tr.tuning_state()
+    assert set(state['dgrad']) <= set(held['dgrad']) and set(state['wgrad']) <= set(held['wgrad'])     # the foreign entries are there ...
     lp = tr.train_step(xt, lt, update=False)                             # ... and never applied (99 is refused)
     *_, tra = _setup(cuda, dtype=dtype)
     la = tra.train_step(xt, lt, update=False)

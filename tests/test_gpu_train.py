@@ -472,3 +472,57 @@ def test_two_stream_step_every_bn_backward_consistent(cuda):
             if bool(off.any()):
                 bad.append((it, c.name, int(off.sum()), int((dy[off] == 0).sum())))
     assert not bad, bad
+
+
+@pytest.fixture(scope='module')
+def tuned(cuda):
+    """One tune='measure' bf16 net + Trainer of the micro spec, shared by the cases below and released with the module: the choices
+    of its inference plan and of one training step, its launch list, inference logits and training losses under them."""
+    from yolo_amd.net import CarNet
+    from yolo_amd.train import Trainer
+    spec, size = og.spec_micro(), (64, 96)
+    P = og.init_params(og.build_graph(spec), seed=0, bn='random')
+    x = torch.from_numpy(np.random.default_rng(2).random((2, 3) + size, dtype=np.float32)).to(cuda)
+    lab = torch.from_numpy(ot.synthetic_labels(2, seed=1, render_rate=0.0, num_class=4)).to(cuda)
+    net = CarNet(spec, dtype='bf16', device=cuda, tune='measure').load_params(P)
+    tr = Trainer(net, size)
+    net(x)                                                # (the inference plan's shapes are measured before the state is taken)
+    state = tr.tune(x, lab)
+    logits = [o.clone() for o in net(x)]
+    losses = tr.train_step(x, lab, update=False).clone()
+    return dict(spec=spec, size=size, P=P, x=x, lab=lab, state=state, logits=logits, losses=losses,
+                signature=net.plan_signature(2, *size), train_logits=tr.merged_logits().clone())
+
+
+@pytest.mark.parametrize('mode', ['measure', 'plan'])
+def test_tuning_state_pins_a_fresh_net_and_trainer(cuda, tmp_path, tuned, mode):
+    """The choices one net + Trainer measured, handed to a fresh pair -- tune='measure' + load_tuning_state, or tune='plan' on a
+    plan file written from them --: nothing is measured again, nothing is stale, the same launch list, bit-identical inference
+    logits, training-mode logits and losses."""
+    from yolo_amd.net import CarNet
+    from yolo_amd.train import Trainer
+    from yolo_amd import plans
+    t = tuned
+    state = t['state']
+    assert all(state[s] for s in plans.SECTIONS)
+    if mode == 'plan':
+        path = str(tmp_path / 'plan.json')
+        plans.save(path, state)
+        fresh = CarNet(t['spec'], dtype='bf16', device=cuda, tune='plan', tune_cache=path).load_params(t['P'])
+        ftr = Trainer(fresh, t['size'])
+        assert fresh.plan_meta['md5'] == plans.md5(state)
+    else:
+        fresh = CarNet(t['spec'], dtype='bf16', device=cuda, tune='measure').load_params(t['P'])
+        ftr = Trainer(fresh, t['size'])
+        assert ftr.tuning_state() == {s: {} for s in plans.SECTIONS}
+        ftr.load_tuning_state(state)
+    assert fresh.tune == mode
+    logits = [o.clone() for o in fresh(t['x'])]
+    losses = ftr.train_step(t['x'], t['lab'], update=False)
+    torch.cuda.synchronize()
+    assert plans.new_keys(ftr.tuning_state(), state) == 0 and plans.new_keys(fresh.tuning_state(), state) == 0
+    assert fresh.stale_choices == 0
+    assert fresh.plan_signature(2, *t['size']) == t['signature']
+    assert all(torch.equal(a, b) for a, b in zip(logits, t['logits']))
+    assert torch.equal(ftr.merged_logits(), t['train_logits'])
+    assert torch.equal(losses, t['losses'])

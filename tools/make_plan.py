@@ -31,7 +31,7 @@ if a.base:
     bstate, bmeta = plans.load(a.base)
     from yolo_amd import lib as L_
     drop = {{'f32': L_.F32, 'bf16': L_.BF16, 'f16': L_.F16, 'bf16x3': L_.BF16X3, 'f16x3': L_.F16X3}[d_] for d_ in a.remeasure.split(',') if d_}
-    # (a forward conv key is (N, H, W, Cin, Cout, ksize, stride, out_f32, residual, dtype, ...): plans of net.py _measure_algo)
+    # (a forward conv key is (N, H, W, Cin, Cout, ksize, stride, out_f32, residual, dtype, ...): yolo_amd/tuner.py conv_key)
     bstate['algo'] = {k: v for k, v in bstate['algo'].items() if not (isinstance(k[0], int) and len(k) >= 10 and k[9] in drop)}
     states.append(bstate)
     base_workloads = list(bmeta.get('workloads', []))

@@ -6,13 +6,13 @@ fine->coarse, each (B, H_i*W_i, A, C) float32.  Every arithmetic op runs in liby
 (hand-written HIP for gfx950); torch only owns device memory and the stream.
 """
 import ctypes as C
-import json
 import os
 
 import numpy as np
 import torch
 
 from . import lib as L
+from .tuner import Tuner
 from .spec import NetGraph, BN_EPS, LEAKY_SLOPE, xavier_bound
 
 _TORCH_DT = {'bf16': torch.bfloat16, 'f16': torch.float16, 'f32': torch.float32, 'bf16x3': torch.bfloat16, 'f16x3': torch.float16}
@@ -59,15 +59,11 @@ class CarNet(object):
         # (round 6) 'plan' = launch the kernels of a SHIPPED plan file (yolo_amd/plans.py; default profiles/plan.json -- the set
         # bench.py runs and the parity tests compare with the oracle): every layer shape the plan holds gets its variant, a shape it
         # does not hold gets the heuristic's; nothing is ever timed.  What a deployment wants: the same kernels on every box.
-        if tune not in ('auto', 'measure', 'plan'):
-            raise ValueError("tune must be 'auto', 'measure' or 'plan'")
-        self.measure_live = tune == 'measure'      # a shape without a cached choice is timed ('measure') or left to the heuristic ('plan')
-        self._plan_state = None
-        if tune == 'plan':
-            from . import plans
-            self._plan_state, self.plan_meta = plans.load(tune_cache or plans.DEFAULT)
-            tune, tune_cache = 'measure', None       # (from here on: the cached-choice code paths of 'measure', minus the timing)
+        # The policy and the choices live in self.tuner (yolo_amd/tuner.py), which the Trainer of this net shares; tune_cache: the
+        # plan file of 'plan', an optional JSON file remembering the choices of 'measure'.
         self.tune = tune
+        self.tuner = Tuner(tune, tune_cache, valid=lambda d: self._lib.yolo_conv_kernel_name(C.byref(d), C.create_string_buffer(256), 256) == 0)
+        self.plan_meta = self.tuner.plan_meta        # (the plan file's meta block; None unless tune='plan')
         # fuse_stem: run the stem and the first down-sampling conv as one kernel where yolo_stem_down_fwd takes the
         # shape (32 -> 64, bf16); the stem's own output is then not materialised (no 'stem' parity tap)
         self.fuse_stem = bool(fuse_stem)
@@ -92,18 +88,9 @@ class CarNet(object):
         # (measured, round 4: -3..-16 us per pair in isolation, nothing in the whole pass -- so it is only considered where the
         #  tuner can check it, i.e. with tune='measure')
         self._force_tail = fuse_tail == 'force'
-        self.fuse_tail = bool(fuse_tail) and (tune == 'measure' or fuse_tail == 'force')      # ('force': tests -- every eligible pair)
-        if fuse_tail is True and tune != 'measure' and fuse_tail != 'force':
-            self.fuse_tail_note = "fuse_tail=True has no effect under tune='auto' (pairs are only fused where the tuner measured a gain)"
-        else:
-            self.fuse_tail_note = None
-        self._algo_cache = dict(self._plan_state['algo']) if self._plan_state is not None else {}
-        self.stale_choices = 0      # adopted choices (plan file / rank 0) this library no longer takes: dropped and measured again
-        # optional JSON file remembering measured choices (so a profiled run launches only the chosen kernels)
-        self._tune_cache = tune_cache
-        if tune_cache and os.path.exists(tune_cache):
-            with open(tune_cache) as f:
-                self._algo_cache = {tuple(json.loads(k)): v for k, v in json.load(f).items()}
+        self.fuse_tail = bool(fuse_tail) and (self.tuner.applies or self._force_tail)      # ('force': tests -- every eligible pair)
+        self.fuse_tail_note = ("fuse_tail=True has no effect under tune='auto' (pairs are only fused where the tuner measured a gain)"
+                               if fuse_tail is True and not self.tuner.applies else None)
         self.params = {}
         self._prepared = {}
         self._plans = {}
@@ -250,8 +237,7 @@ class CarNet(object):
             d.algo = self._tail_algo(d)
             plan.ops.append(('conv', d, c.name + '+' + tail[0].name))
         else:
-            if self.tune == 'measure':
-                d.algo = self._measure_algo(d)
+            d.algo = self._algo(d)
             plan.ops.append(('conv', d, c.name))
         oshape = (N, 2 * ho, 2 * wo, c.cout) if up2 else (N, ho, wo, c.cout)
         if not isinstance(out, int):
@@ -283,10 +269,7 @@ class CarNet(object):
 
     def _tail_algo(self, d):
         """The 256-cout tile variant of a fused launch: the first the library takes, or (tune='measure') the fastest."""
-        cands = self.TAIL_ALGOS[d.stride]
-        if self.tune != 'measure':
-            return 0
-        return self._measure_algo(d, algos=cands, key_extra=('tail', d.tail_cout, d.tail_out_f32))
+        return self._algo(d, algos=self.TAIL_ALGOS[d.stride], key_extra=('tail', d.tail_cout, d.tail_out_f32))
 
     def _use_tail(self, c3, c1, x, xshape, residual, out, out1, out1_f32=False, t_bs=0, t_ps=0, y_bs=0, y_ps=0):
         """Whether (3x3 c3, then 1x1 c1 on its output) runs as ONE fused launch.  fuse_tail='force' (tests): whenever the library
@@ -299,43 +282,18 @@ class CarNet(object):
         ho, wo = c3.out_hw(H, W)
         d = self._conv_desc(c3, x, xshape, out, residual, False, y_bs, y_ps)
         self._set_tail(d, c1, out1, out1_f32, t_bs, t_ps)
-        buf = C.create_string_buffer(256)
-        if lib.yolo_conv_kernel_name(C.byref(d), buf, 256) != 0:
+        if lib.yolo_conv_kernel_name(C.byref(d), C.create_string_buffer(256), 256) != 0:
             return False
-        if self.tune != 'measure' or self._force_tail:
+        if self._force_tail:
             return True
-        key = self._tail_key(d)
-        if key in self._algo_cache:
-            return bool(self._algo_cache[key])
-        if not self.measure_live:
-            return False                                  # (tune='plan': pairs are fused only where the plan says a measurement found a gain)
-        d3 = self._conv_desc(c3, x, xshape, out, residual, False, y_bs, y_ps)
-        d3.algo = self._measure_algo(d3)
-        d1 = self._conv_desc(c1, out, (N, ho, wo, c3.cout), out1, None, out1_f32, t_bs, t_ps)
-        d1.algo = self._measure_algo(d1)
-        d.algo = self._tail_algo(d)
 
-        def timed(fn, n=20):
-            best = float('inf')
-            for _ in range(3):
-                fn(); fn()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(n):
-                    fn()
-                e1.record()
-                e1.synchronize()
-                best = min(best, e0.elapsed_time(e1) / n)
-            return best
-
-        def separate():
-            L.check(lib.yolo_conv_fwd(C.byref(d3), st), 'conv')
-            L.check(lib.yolo_conv_fwd(C.byref(d1), st), 'conv')
-
-        use = lib.yolo_conv_fwd(C.byref(d), st) == 0 and timed(lambda: lib.yolo_conv_fwd(C.byref(d), st)) < timed(separate)
-        self._algo_cache[key] = int(use)
-        self._save_tune_cache()
-        return use
+        def setup():
+            d3 = self._conv_desc(c3, x, xshape, out, residual, False, y_bs, y_ps)
+            d1 = self._conv_desc(c1, out, (N, ho, wo, c3.cout), out1, None, out1_f32, t_bs, t_ps)
+            d3.algo, d1.algo, d.algo = self._algo(d3), self._algo(d1), self._tail_algo(d)
+            return (lambda: lib.yolo_conv_fwd(C.byref(d), st)), self._separate(d3, d1)
+        # (default False -- tune='plan': pairs are fused only where the plan says a measurement found a gain; best of three windows)
+        return self.tuner.fused(self._tail_key(d), False, setup, windows=3)
 
     def _res_block_payload(self, c1, c2, x, out, shp):
         wp1, s1, b1 = self._prepared[c1.name]
@@ -352,61 +310,49 @@ class CarNet(object):
         C_ = shp[3]
         if not self._res_block_eligible(c1, c2):
             return False
-        if self.tune != 'measure':
-            return True
-        key = ('res', shp[0], shp[1], shp[2], C_, _LIB_DT[self.dtype])
-        if key in self._algo_cache:
-            return bool(self._algo_cache[key])
-        if not self.measure_live:
-            return True                                   # (tune='plan', unknown shape: the heuristic's answer, as under tune='auto')
-        lib, st, dt = self._lib, L.stream_ptr(), _LIB_DT[self.dtype]
-        tdt = _TORCH_DT[self.dtype]
-        mid = torch.empty(shp[:3] + (C_ // 2,), dtype=tdt, device=self.device)
-        out = torch.empty(shp, dtype=tdt, device=self.device)
-        d1 = self._conv_desc(c1, x, shp, mid)
-        d2 = self._conv_desc(c2, mid, shp[:3] + (C_ // 2,), out, residual=x)
-        d1.algo, d2.algo = self._measure_algo(d1), self._measure_algo(d2)
-        pay = self._res_block_payload(c1, c2, x, out, shp)
+        dt = _LIB_DT[self.dtype]
 
-        def timed(fn, n=20):
-            fn(); fn()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(n):
-                fn()
-            e1.record()
-            e1.synchronize()
-            return e0.elapsed_time(e1) / n
+        def setup():
+            lib, st, tdt = self._lib, L.stream_ptr(), _TORCH_DT[self.dtype]
+            mid = torch.empty(shp[:3] + (C_ // 2,), dtype=tdt, device=self.device)
+            out = torch.empty(shp, dtype=tdt, device=self.device)
+            d1 = self._conv_desc(c1, x, shp, mid)
+            d2 = self._conv_desc(c2, mid, shp[:3] + (C_ // 2,), out, residual=x)
+            d1.algo, d2.algo = self._algo(d1), self._algo(d2)
+            pay = self._res_block_payload(c1, c2, x, out, shp)
+            # (pay, d1 and d2 hold raw pointers: both closures own the scratch tensors their launches write)
+            return (lambda own=(mid, out): lib.yolo_res_block_fwd(*pay, dt, LEAKY_SLOPE, st)), self._separate(d1, d2, own=(mid, out))
+        # (default True -- tune='plan', unknown shape: the heuristic's answer, as under tune='auto')
+        return self.tuner.fused(('res', shp[0], shp[1], shp[2], C_, dt), True, setup)
 
-        def separate():
-            L.check(lib.yolo_conv_fwd(C.byref(d1), st), 'conv')
-            L.check(lib.yolo_conv_fwd(C.byref(d2), st), 'conv')
+    def _separate(self, da, db, own=None):
+        """A launch closure: the two convolutions a fused kernel is timed against, one after the other (own: tensors it keeps alive)."""
+        lib, st = self._lib, L.stream_ptr()
 
-        fused_ok = lib.yolo_res_block_fwd(*pay, dt, LEAKY_SLOPE, st) == 0
-        use = fused_ok and timed(lambda: lib.yolo_res_block_fwd(*pay, dt, LEAKY_SLOPE, st)) < timed(separate)
-        self._algo_cache[key] = int(use)
-        self._save_tune_cache()
-        return use
+        def run(own=own):
+            L.check(lib.yolo_conv_fwd(C.byref(da), st), 'conv')
+            L.check(lib.yolo_conv_fwd(C.byref(db), st), 'conv')
+        return run
 
     # ---- measured kernel choices as a value (N > 1: rank 0 measures, every rank runs rank 0's plan) ----------------
     def tuning_state(self):
-        """The measured per-shape kernel choices (tune='measure') as a picklable dict."""
-        return {'algo': dict(self._algo_cache)}
+        """The per-shape forward kernel choices (tune='measure' / 'plan') as a picklable dict: the 'algo' section only."""
+        return self.tuner.state(('algo',))
 
     def load_tuning_state(self, state):
         """Adopt another rank's choices: shapes found here are not measured again, so a plan built afterwards launches the
         same kernel instantiations as on the rank the state came from (parallel.share_tuning)."""
-        self._algo_cache.update(state['algo'])
+        self.tuner.load(state, ('algo',))
         return self
+
+    @property
+    def stale_choices(self):
+        """Adopted choices (plan file / rank 0) this library no longer takes: dropped, and measured again under tune='measure'."""
+        return self.tuner.stale
 
     def plan_signature(self, B, H, W):
         """[(op, kernel instantiation)] of the launch plan for one input shape -- what must agree across ranks."""
         return [(n, k) for n, k, _ in self.plan_kernels(B, H, W)]
-
-    def _save_tune_cache(self):
-        if self._tune_cache:
-            with open(self._tune_cache, 'w') as f:
-                json.dump({json.dumps(list(k)): v for k, v in self._algo_cache.items()}, f)
 
     def _conv_desc(self, c, x, xshape, out, residual=None, out_f32=False, y_bs=0, y_ps=0, cin=None, x_ps=0, up2=False):
         N, H, W, _ = xshape
@@ -438,71 +384,18 @@ class CarNet(object):
         d.x_lo_offset, d.y_lo_offset = x_lo, y_lo
         return d
 
-    def _measure_algo(self, d, iters=5, fn=None, algos=None, key_extra=()):
-        """Fastest conv variant for this layer shape (cached).  Outputs are overwritten while timing,
-        which is harmless: the plan has not run yet.  fn / algos: another entry point taking the same descriptor
-        (yolo_conv_dgrad_s2, with d.ksize = 2 as the cache key's mark) and its variant ids; 1 = none ran."""
-        key = (d.N, d.H, d.W, d.Cin, d.Cout, d.ksize, d.stride, d.out_f32, bool(d.residual), d.dtype)
-        if d.x_pixel_stride or d.upsample2x or (d.y_pixel_stride and not d.out_f32):
-            key = key + (int(d.x_pixel_stride), int(d.upsample2x), int(d.y_pixel_stride))
-        key = key + tuple(key_extra)
+    def _algo(self, d, algos=None, key_extra=()):
+        """The tuner's variant for this forward conv (0 under tune='auto': the library's heuristic).  When it is measured, the
+        outputs are overwritten, which is harmless: the plan has not run yet."""
         lib, st = self._lib, L.stream_ptr()
-        if key in self._algo_cache:
-            # a choice adopted from a plan file / another rank: dry-run it (host only, no launch) -- a library built after the
-            # plan was made may no longer take that variant for the shape (a tile's halo budget changed, an id was retired); such
-            # an entry is dropped and the shape measured again, which plans.new_keys() then counts as measured live
-            cached = self._algo_cache[key]
-            if fn is None and cached != 1:
-                d.algo = cached
-                ok = lib.yolo_conv_kernel_name(C.byref(d), C.create_string_buffer(256), 256) == 0
-                d.algo = 0
-                if not ok:
-                    del self._algo_cache[key]
-                    self.stale_choices += 1
-            if key in self._algo_cache:
-                return cached
-        if not self.measure_live:
-            return 0                                      # (tune='plan', a shape the plan does not hold: the library's heuristic)
-        fn = fn or lib.yolo_conv_fwd
-
-        def time_algo(algo, n):
-            d.algo = algo
-            if fn(C.byref(d), st) != 0:
-                return None
-            fn(C.byref(d), st)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(n):
-                fn(C.byref(d), st)
-            e1.record()
-            e1.synchronize()
-            return e0.elapsed_time(e1) / n
-
-        # two passes: a short one over every variant, then the three fastest again with 4x the launches -- a single
-        # short timing is noisy enough (DVFS, neighbours' tails) to pick a variant that is 5 % slower
-        # (round 3: the second pass INTERLEAVES its candidates over three rounds and keeps each one's fastest round -- timed one
-        #  after the other, a clock / power drift of a few per cent between two candidates' windows picked the slower one: the
-        #  64 -> 128 stride-2 layer at 608x608 ran the generic kernel, 446 us, where the streaming one takes 417)
-        top, mult, rounds = 3, 2, 3
-        first = [(t, a) for a in (algos or self.ALGOS) for t in [time_algo(a, iters)] if t is not None]
-        first.sort()
-        cands = [a for _, a in first[:top]]
-        fastest = {a: float('inf') for a in cands}
-        for _ in range(rounds):
-            for algo in cands:
-                t = time_algo(algo, mult * iters)
-                if t is not None:
-                    fastest[algo] = min(fastest[algo], t)
-        best = min(cands, key=lambda a_: fastest[a_]) if cands else 1
-        d.algo = 0
-        self._algo_cache[key] = best
-        self._save_tune_cache()
-        return best
+        return self.tuner.conv(d, algos or self.ALGOS, lambda: lib.yolo_conv_fwd(C.byref(d), st), key_extra)
 
     def _stage_ops(self, plan, down, res, x, shp, cat_view, down_done, tdt):
         """The launch list of one backbone stage (down-sampling conv + residual blocks) appended to `plan`: the fused
         residual-block kernel wherever it is eligible and chosen; elsewhere a conv carries the next block's 1x1 as a fused tail
-        when the pair is measured faster (_use_tail)."""
+        when the pair is measured faster (_use_tail).  (Round 4 also measured, for the stage where both fusions apply -- D53's
+        stage 1 --, a chain of fused tails INSTEAD of the residual-block kernel: 620-730 us against 448 us per 3x3 + 1x1 pair at
+        152x152 bs 64, because the 8-wave tiles that can carry a tail are the slow ones for K = 576.  Not offered to the tuner.)"""
         pre_mid = None
 
         def tail_for(c3, xin, xshp, resid, j_next, out=None):
@@ -541,11 +434,13 @@ class CarNet(object):
             x, shp = self._conv_op(plan, c2, mid, mshp, residual=x, out=cat_view if last else None, tail=tl)
         return x, shp
 
-    def _build_stage(self, plan, down, res, x, shp, cat_view, down_done, tdt):
-        """One backbone stage.  (Round 4 also measured, for the stage where both fusions apply -- D53's stage 1 --, a chain of
-        fused tails INSTEAD of the residual-block kernel: 620-730 us against 448 us per 3x3 + 1x1 pair at 152x152 bs 64, because
-        the 8-wave tiles that can carry a tail are the slow ones for K = 576.  Not offered to the tuner.)"""
-        return self._stage_ops(plan, down, res, x, shp, cat_view, down_done, tdt)
+    def _plan_for(self, B, H, W):
+        """The launch plan of one input shape, built (from freshly prepared weights) on first use."""
+        self._ensure_prepared()
+        plan = self._plans.get((B, H, W))
+        if plan is None:
+            plan = self._plans[(B, H, W)] = self._build_plan(B, H, W)
+        return plan
 
     def _build_plan(self, B, H, W):
         g = self.graph
@@ -598,7 +493,7 @@ class CarNet(object):
                 plan.buffers.append(cat)
                 cats[i] = (cat, up_ch)
                 cat_view = cat[..., up_ch:]
-            x, shp = self._build_stage(plan, down, res, x, shp, cat_view, down is fused_down, tdt)
+            x, shp = self._stage_ops(plan, down, res, x, shp, cat_view, down is fused_down, tdt)
             if i >= nst - g.num_pyramid:
                 routes.append((x, shp, cats.get(i)))
         # merged head buffer (B, sum HW, A*C) float32, scales fine->coarse (car/utils.py:95, car/YOLO.py:841)
@@ -686,7 +581,6 @@ class CarNet(object):
             tr = self.trainer((int(x.shape[2]), int(x.shape[3])))
             return tr.forward(x)
         L.require_current_device(self.device, 'this CarNet')
-        self._ensure_prepared()
         if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32 or not x.is_cuda:
             raise ValueError('expected a (B,3,H,W) float32 CUDA tensor')
         x = x.contiguous()
@@ -695,10 +589,7 @@ class CarNet(object):
         if H % down or W % down:
             # (the reference fails in F.concat for such sizes: the up-sampled map no longer matches its route)
             raise ValueError('image size %dx%d is not a multiple of the total stride %d' % (H, W, down))
-        key = (B, H, W)
-        plan = self._plans.get(key)
-        if plan is None:
-            plan = self._plans[key] = self._build_plan(B, H, W)
+        plan = self._plan_for(B, H, W)
         lib, st, dt = self._lib, L.stream_ptr(), _LIB_DT[self.dtype]
         if plan.x_nhwc is not None:
             L.check(lib.yolo_nchw_to_nhwc(x.data_ptr(), L.ptr(plan.x_nhwc), B, 3, H, W, 8, dt, st), 'nchw_to_nhwc')
@@ -782,10 +673,7 @@ class CarNet(object):
     def plan_kernels(self, B, H, W):
         """[(op name, kernel instantiation name, algorithmic FLOPs)] for the launch list of one input
         shape (FLOPs = 2*Cin*k^2*Cout*Ho*Wo*B per conv; 0 for non-conv ops)."""
-        self._ensure_prepared()
-        plan = self._plans.get((B, H, W))
-        if plan is None:
-            plan = self._plans[(B, H, W)] = self._build_plan(B, H, W)
+        plan = self._plan_for(B, H, W)
         by_name = {c.name: c for c in self.graph.convs()}
         out = []
         buf = C.create_string_buffer(256)
@@ -821,9 +709,7 @@ class CarNet(object):
         """{op name: ALGORITHMIC HBM bytes of that launch} for the conv launches of one input shape: input read once + output
         written once (+ the residual read once) + weights once (SURVEY section 8d's per-layer roofline convention; a fused tail adds
         its own output and weights, its input never leaves the chip) -- the figure `roofline.traffic` is compared with."""
-        self._ensure_prepared()
-        self.plan_kernels(B, H, W)
-        plan = self._plans[(B, H, W)]
+        plan = self._plan_for(B, H, W)
         by_name = {c.name: c for c in self.graph.convs()}
         es = 2 if self.dtype in ('bf16', 'f16') else 4       # (split types: two 2-byte planes per value, weights as a hi + lo pair)
         out = {}
@@ -848,7 +734,7 @@ class CarNet(object):
         """forward() that brackets every launch with a pair of torch CUDA events (recorded on the
         stream the kernels run on).  events: list that receives (op name, start, end)."""
         B, _, H, W = x.shape
-        plan = self._plans[(B, H, W)]
+        plan = self._plan_for(B, H, W)
         lib, st, dt = self._lib, L.stream_ptr(), _LIB_DT[self.dtype]
         if plan.x_nhwc is not None:
             L.check(lib.yolo_nchw_to_nhwc(x.data_ptr(), L.ptr(plan.x_nhwc), B, 3, H, W, 8, dt, st), 'nchw_to_nhwc')

@@ -63,6 +63,7 @@ class Trainer(object):
         # choices, so every other dtype keys its own choices by its name (a bf16 algo id would be refused on an f32 or split conv)
         self._key_tag = () if self.ldt == L.BF16 else (net.dtype,)
         self.lib, self.dev = net._lib, net.device
+        self.tuner = net.tuner              # the kernel choices of all three sections and the tune mode, shared with the net
         self.scale = dict(DEFAULT_SCALE if scale is None else scale)
         self.lr, self.b1, self.b2, self.eps = learning_rate, beta1, beta2, eps
         self.pos_w, self.neg_w, self.car_rotate = positive_weight, negative_weight, car_rotate
@@ -109,11 +110,6 @@ class Trainer(object):
         self._prep = {}             # conv name -> _Prep
         self._s2_retired = []
         self._plans = {}
-        self._dgrad_algo = {}
-        self._wgrad_algo = {}
-        if getattr(net, '_plan_state', None) is not None:      # CarNet(tune='plan'): the plan's data- and weight-gradient choices too
-            self._dgrad_algo.update(net._plan_state['dgrad'])
-            self._wgrad_algo.update(net._plan_state['wgrad'])
         self._fwd_B = None
         cmax = max(c.cout for c in g.convs())
         # two BatchNorm workspaces used alternately (the *_pp BatchNorm entries: a call leaves its own dirty and zeroes the next one's)
@@ -135,10 +131,6 @@ class Trainer(object):
         self._side = torch.cuda.Stream(device=self.dev)
         self._repack()
         self._packed_version = net._version
-
-    @property
-    def _measure(self):
-        return getattr(self.net, 'tune', None) == 'measure'
 
     def resized(self, size):
         """A Trainer for another image size with THIS one's hyper-parameters and optimiser state (Adam moments, update count):
@@ -257,10 +249,6 @@ class Trainer(object):
         """A plan activation; split path: with the buffer of its gradient's first contribution (grad=False: it receives none)."""
         return _T(self._buf(shape), tuple(shape), gbuf=self._buf(shape) if (self.split and grad) else None)
 
-    def _zeroed(self, shape):
-        """A zeroed activation-shaped scratch buffer (timing runs only)."""
-        return self._buf(shape) if self.split else torch.zeros(shape, dtype=self.tdt, device=self.dev)
-
     def _grad_out(self, t):
         """Where the first contribution to d(loss)/d(t) is written."""
         return t.gbuf if self.split else torch.empty(t.shape, dtype=self.tdt, device=self.dev)
@@ -296,11 +284,11 @@ class Trainer(object):
         d.y_batch_stride, d.y_pixel_stride, d.algo = y_bs, y_ps, 0
         return d
 
-    def _tune(self, d):
-        """Pick the conv variant by measurement when the net was built with tune='measure' (the timing runs only
-        overwrite d.y, which nothing has consumed yet)."""
-        if self._measure:
-            d.algo = self.net._measure_algo(d)
+    def _algo(self, d, fn=None, algos=None):
+        """The tuner's variant for a forward conv or -- same keys, same cache -- a data gradient (0 under tune='auto'; a timing run overwrites
+        d.y).  fn / algos: another entry point taking d (yolo_conv_dgrad_s2, d.ksize = 2 as the key's mark) and its ids; 1 = none ran."""
+        st, run = L.stream_ptr(), fn or self.lib.yolo_conv_fwd
+        return self.tuner.conv(d, algos or self.net.ALGOS, lambda: run(C.byref(d), st), dry_run=fn is None)
 
     def _build(self, B, H, W):
         g, lib = self.net.graph, self.lib
@@ -326,7 +314,7 @@ class Trainer(object):
             invstd = torch.empty_like(mean)
             # raw convolution: identity epilogue
             d = self._conv_desc(xin.val, xin.shape, self._prep[c.name].wp, None, None, yraw.val, Cc, c.cout, c.k, c.stride)
-            self._tune(d)
+            d.algo = self._algo(d)
             op = dict(kind='conv_bn', c=c, x=xin, yraw=yraw, z=z, mean=mean, invstd=invstd, res=residual, desc=d, srows=0)
             if self.split:
                 # the plan owns every gradient buffer of the split path: d(loss)/d(yraw) and, for a stride-2 conv, its dilated copy
@@ -350,7 +338,7 @@ class Trainer(object):
             # an output conv writes fp32 logits at y; src: its slice of d(loss)/d(logits) as (pointer, batch stride, pixel stride)
             r = self._prep[c.name]
             d = self._conv_desc(t.val, t.shape, r.wp, r.ones, r.bias, y, c.cin, c.cout, 1, 1, out_f32=1, y_bs=y_bs, y_ps=y_ps)
-            self._tune(d)
+            d.algo = self._algo(d)
             cpad = (c.cout + 7) // 8 * 8
             P.fwd.append(dict(kind='out', c=c, x=t, desc=d, hw=hw_, cpad=cpad, src=src, dyp=self._buf((B * hw_, cpad))))
 
@@ -541,6 +529,20 @@ class Trainer(object):
         else:
             self._add(t.grad, src, t.shape, L.stream_ptr())
 
+    def _dgrad_choice(self, key, d, shape, fn=None, algos=None):
+        """The tuner's variant for data-gradient descriptor d, kept under the Trainer-level `key` (asked in every step).  A shape without one goes through
+        _algo as a copy of d that writes (where d accumulates: adds to) a zeroed scratch buffer of `shape`: the real output may hold a gradient."""
+        if not self.tuner.applies:
+            return 0
+
+        def conv():
+            dm = L.ConvDesc.from_buffer_copy(d)
+            buf = self._buf(shape) if self.split else torch.zeros(shape, dtype=self.tdt, device=self.dev)
+            dm.y = L.ptr(buf)
+            dm.residual = L.ptr(buf) if d.residual else None
+            return self._algo(dm, fn, algos)
+        return self.tuner.dgrad(key, conv)
+
     def _dgrad(self, c, dy, dy_shape, xin, cin_of_dy):
         """grad[xin] (+)= data gradient of conv c given dy (N,Ho,Wo,cin_of_dy) (dense).  Identity epilogues throughout."""
         lib, st = self.lib, L.stream_ptr()
@@ -553,19 +555,8 @@ class Trainer(object):
             else:
                 out, resid = xin.grad, xin.grad
             d = self._conv_desc(dy, dy_shape, r.s2, None, None, out, cin_of_dy, 4 * Cx, 2, 1, residual=resid)
-            rc = None
-            if self._measure:
-                key = ('s2', dy_shape, cin_of_dy, Cx, resid is not None)
-                if key not in self._dgrad_algo:
-                    scratch = torch.zeros(xin.shape, dtype=self.tdt, device=self.dev)
-                    dm = self._conv_desc(dy, dy_shape, r.s2, None, None, scratch, cin_of_dy, 4 * Cx, 2, 1,
-                                         residual=scratch if resid is not None else None)
-                    self._dgrad_algo[key] = self.net._measure_algo(dm, fn=lib.yolo_conv_dgrad_s2, algos=(2, 6, 10, 4))
-                d.algo = self._dgrad_algo[key]
-                if d.algo == 1:
-                    rc = L.EUNSUPPORTED
-            if rc is None:
-                rc = lib.yolo_conv_dgrad_s2(C.byref(d), st)
+            d.algo = self._dgrad_choice(('s2', dy_shape, cin_of_dy, Cx, resid is not None), d, xin.shape, lib.yolo_conv_dgrad_s2, (2, 6, 10, 4))
+            rc = L.EUNSUPPORTED if d.algo == 1 else lib.yolo_conv_dgrad_s2(C.byref(d), st)
             if rc == 0:
                 xin.grad, xin.ready = out, True
                 xin.ngot += 1
@@ -585,55 +576,29 @@ class Trainer(object):
         else:
             out, resid = xin.grad, xin.grad
         d = self._conv_desc(src, sshape, r.wd, None, None, out, cin_of_dy, Cx, c.k, 1, residual=resid)
-        if self._measure:
-            key = self._key_tag + (sshape, cin_of_dy, Cx, c.k, resid is not None)
-            if key not in self._dgrad_algo:
-                # time the variants on scratch outputs: the real `out` may already hold an accumulated gradient
-                scratch = self._zeroed(xin.shape)
-                dm = self._conv_desc(src, sshape, r.wd, None, None, scratch, cin_of_dy, Cx, c.k, 1,
-                                     residual=scratch if resid is not None else None)
-                self._dgrad_algo[key] = self.net._measure_algo(dm)
-            d.algo = self._dgrad_algo[key]
+        d.algo = self._dgrad_choice(self._key_tag + (sshape, cin_of_dy, Cx, c.k, resid is not None), d, xin.shape)
         L.check(lib.yolo_conv_fwd(C.byref(d), st), 'dgrad ' + c.name)
         xin.grad, xin.ready = out, True
         xin.ngot += 1
 
     def _wgrad_algo_for(self, c, dy, xin):
-        """Weight-gradient algo id for conv c: 0 (the library's choice) unless the net was built with tune='measure' -- then the
-        fastest of the kernels that take the shape, timed once per layer shape on a scratch gradient (the 8-wave row walk wins
+        """Weight-gradient algo id for conv c: 0 (the library's choice) unless the tuner holds or -- tune='measure' -- measures one:
+        the fastest of the kernels that take the shape, timed once per layer shape on a scratch gradient (the 8-wave row walk wins
         on two D53 shapes, the 16-column walker on the 13x13 ones, ...)."""
-        if not self._measure or self.ldt == L.F32:
+        if self.ldt == L.F32 or not self.tuner.applies:
             return 0
         N, Hh, Ww, Cx = xin.shape
-        key = self._key_tag + (N, Hh, Ww, Cx, c.cout, c.k, c.stride)
-        if key not in self._wgrad_algo and not getattr(self.net, 'measure_live', True):
-            return 0                                      # (tune='plan', a shape the plan does not hold: the library's choice)
-        if key not in self._wgrad_algo:
-            cands = self._wgrad_algos(c)
-            best, best_t = 0, float('inf')
-            if len(cands) > 1:
-                st = L.stream_ptr()
-                # the candidates run on THIS stream with the workspace the side stream's weight gradients share (their
-                # finishing passes accumulate into it and zero it): nothing of the side stream may be in flight
-                main = torch.cuda.current_stream()
-                main.wait_stream(self._side)
-                scratch = torch.zeros((c.cout, Cx, c.k, c.k), dtype=torch.float32, device=self.dev)
-                for a in cands:
-                    call = self._wgrad_launch(dy, xin.val, scratch, N, Hh, Ww, Cx, c.cout, c.k, c.stride, algo=a)
-                    if call(st) != 0:
-                        continue
-                    call(st)
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(6):
-                        call(st)
-                    e1.record(); e1.synchronize()
-                    t = e0.elapsed_time(e1)
-                    if t < best_t * 0.98:                       # (a later candidate must win by 2 %)
-                        best, best_t = a, t
-                self._side.wait_stream(main)
-            self._wgrad_algo[key] = best
-        return self._wgrad_algo[key]
+
+        def bracket(pick):
+            # the candidates run on THIS stream with the workspace the side stream's weight gradients share (their
+            # finishing passes accumulate into it and zero it): nothing of the side stream may be in flight
+            st, main = L.stream_ptr(), torch.cuda.current_stream()
+            main.wait_stream(self._side)
+            scratch = torch.zeros((c.cout, Cx, c.k, c.k), dtype=torch.float32, device=self.dev)
+            best = pick(lambda a: self._wgrad_launch(dy, xin.val, scratch, N, Hh, Ww, Cx, c.cout, c.k, c.stride, algo=a)(st))
+            self._side.wait_stream(main)
+            return best
+        return self.tuner.wgrad(self._key_tag + (N, Hh, Ww, Cx, c.cout, c.k, c.stride), self._wgrad_algos(c), bracket)
 
     def _wgrad(self, dy, names, launch):
         """Run launch(stream) -- a weight-gradient call reading dy, which the current stream has just produced -- on the
@@ -884,12 +849,10 @@ class Trainer(object):
 
     # ---- measured kernel choices as a value (N > 1: rank 0 measures, every rank runs rank 0's plan) -----------------
     def tuning_state(self):
-        return {'algo': dict(self.net._algo_cache), 'dgrad': dict(self._dgrad_algo), 'wgrad': dict(self._wgrad_algo)}
+        return self.tuner.state()
 
     def load_tuning_state(self, state):
-        self.net._algo_cache.update(state['algo'])
-        self._dgrad_algo.update(state['dgrad'])
-        self._wgrad_algo.update(state['wgrad'])
+        self.tuner.load(state)
         return self
 
     def tune(self, images, labels, lp_labels=None):
