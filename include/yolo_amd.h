@@ -317,6 +317,42 @@ int yolo_plate_stats(const unsigned char* plates, const void* rows, void* worksp
 int yolo_plate_render(const float* bg, const unsigned char* plates, const void* rows, const void* workspace, float* out, int N, int H,
                       int W, void* stream);
 
+/* The background batch of a training step (yolo_modules/yolo_gluon.py:43-97: load_background's mxnet.image.ImageIter with rand_crop,
+ * rand_resize, rand_mirror and the colour jitters, read by ImageIter_next_batch) with the PIXELS made on the device: the host decides
+ * (image, mip level, crop, mirror, colour: yolo_amd/background.py BackgroundBank.draw_params) and hands over one row of
+ * YOLO_BG_ROW_WORDS 32-bit words per OUTPUT image:
+ *   0 has-image (int)      1 h  2 w: the mip level's size (int)      3..6 roi x0, y0, x1, y1 (int; inclusive, in level pixels)     7 unused
+ *   8,9 the level's byte offset in the bank (one 64-bit int)         10..15 a0..a5 (float): output pixel INDEX -> level pixel INDEX
+ *   16..24 A  25..33 D (3x3 row-major, float)   34..36 e (float)     37..39 unused
+ * bank: 4-byte pixels (R, G, B and a pad byte), every image and its mip levels packed densely as (h, w, 4), bank_bytes in all, 4-byte
+ * aligned; rows ON THE DEVICE, 8-byte aligned; out (N,3,H,W) f32 0..255, dense -- what yolo_render_cars takes as bg.
+ * The arithmetic, every operation in fp32, in this order, nothing fused (this is the definition; tests/background_ref.py restates it):
+ *  the sample P(j, i) at output pixel (column j, row i), three channels R, G, B interpolated independently:
+ *   sx = (a0*j + a1*i) + a2;  sy = (a3*j + a4*i) + a5;   x0 = floor(sx), fx = sx - x0;  y0 = floor(sy), fy = sy - y0
+ *   taps a = (y0, x0), b = (y0, x0+1), c = (y0+1, x0), d = (y0+1, x0+1), every INDEX clamped into the roi (replicate: cv2.resize on
+ *   the crop; no tap reads 0, unlike yolo_render_cars'), each read as its byte's float;
+ *   top = a + fx*(b - a);  bot = c + fx*(d - c);  P = top + fy*(bot - top)
+ *  yolo_bg_stats: per image and channel c the sum of P_c over ALL H*W output pixels, each converted to double and added in double,
+ *   as BG_STAT_BLOCKS = 16 partial sums in a fixed order (workspace: yolo_bg_workspace_bytes(N, H, W) bytes, 8-byte aligned,
+ *   caller-owned); no atomics, so the sums do not depend on scheduling.
+ *  yolo_bg_render: sum_c = the image's partials added in index order (double);  mu_c = (float)(sum_c / (double)(H*W));
+ *   k_c = ((D[c][0]*mu_0 + D[c][1]*mu_1) + D[c][2]*mu_2) + e_c
+ *   out_c = ((A[c][0]*P_0 + A[c][1]*P_1) + A[c][2]*P_2) + k_c          (NO clamp and NO / 255: mxnet's augmenters do not clamp, and
+ *   yolo_render_cars clamps at its blend)
+ *  x0 / y0 are limited to +-2^30 before they become integers.  No load leaves the bank whatever a row holds: a row is "no image" if
+ *  has == 0, or its level does not lie inside the bank (offset negative or not a multiple of 4, h or w <= 0, offset + 4 h w beyond
+ *  bank_bytes), or its roi is empty or not inside the level (x0 < 0, y0 < 0, x1 < x0, y1 < y0, x1 >= w, y1 >= h).  For such a row
+ *  P = 0 everywhere -- so mu = 0 and out_c = e_c -- and the bank is not touched.
+ * YOLO_EINVAL: a NULL pointer, a non-positive N, H, W or bank_bytes, a misaligned bank / rows / workspace.  YOLO_EUNSUPPORTED:
+ * H * ceil(W / 4) beyond 2^31.  Validation comes before any launch.  yolo_bg_workspace_bytes returns YOLO_EINVAL for a non-positive
+ * size.  16-byte plane stores when W % 4 == 0 and out is 16-byte aligned, scalar ones otherwise.
+ * yolo_bg_render must follow yolo_bg_stats on the same rows, in stream order. */
+#define YOLO_BG_ROW_WORDS 40
+long long yolo_bg_workspace_bytes(int N, int H, int W);
+int yolo_bg_stats(const unsigned char* bank, long long bank_bytes, const void* rows, void* workspace, int N, int H, int W, void* stream);
+int yolo_bg_render(const unsigned char* bank, long long bank_bytes, const void* rows, const void* workspace, float* out, int N, int H,
+                   int W, void* stream);
+
 /* 2x nearest up-sample of `up` (N,H/2,W/2,C1) + channel concat with `route` (N,H,W,C2) ->
  * (N,H,W,C1+C2), up-sampled channels first: gluoncv _upsample + F.concat, car/utils.py:92-93. */
 int yolo_upsample2x_concat(const void* up, const void* route, void* y, int N, int H, int W,

@@ -20,4 +20,7 @@ def __getattr__(name):
     if name in ('RenderCar', 'SpriteAtlas', 'LPGenerator', 'PlateCamera'):
         from . import render
         return getattr(render, name)
+    if name == 'BackgroundBank':
+        from . import background
+        return background.BackgroundBank
     raise AttributeError(name)
