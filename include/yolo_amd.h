@@ -353,6 +353,40 @@ int yolo_bg_stats(const unsigned char* bank, long long bank_bytes, const void* r
 int yolo_bg_render(const unsigned char* bank, long long bank_bytes, const void* rows, const void* workspace, float* out, int N, int H,
                    int W, void* stream);
 
+/* Anchor fitting: the reference's kmean mode (car/YOLO.py:599-638) and its IoU k-means (yolo_modules/iou_kmeans.py:11-52, get_dis :55-75)
+ * on the device, the restarts side by side and each run to convergence (the reference makes one random start and exactly 10 rounds, and
+ * fails on an empty cluster, iou_kmeans.py:42).  dis_method = 'L2' (:77-79) is not offered: the kmean mode never uses it.
+ * sizes: a device pointer to n rows, row i at sizes + i * stride floats, h = row[0], w = row[1], stride >= 2 -- a label tensor
+ * (B, nobj, 6 + ncls) is read in place from &labels[0][0][3] with stride = 6 + ncls (car/YOLO.py:616).  centroids / init: [h, w] pairs.
+ * The arithmetic, every operation in fp32, in this order, nothing fused (this is the definition; tests/anchor_ref.py restates it):
+ *  row i is VALID iff h and w are finite and > 0 (the -1 of "no object", 0, NaN and inf are not);
+ *  q(i, j) against centroid (ch, cw) (iou_kmeans.py:68-74):   ih = min(h, ch);  iw = min(w, cw);  inter = ih * iw;
+ *   union = (h * w + ch * cw) - inter;   q = inter / union  (IEEE division)
+ *  assignment: a_i = the lowest j with the largest q -- start from j = 0, replace only on q > best (the argmin of 1 / iou,
+ *   iou_kmeans.py:32, is the same rule); q_i = that q; an invalid row has a_i = -1, q_i = 0 and is counted nowhere
+ *  update (iou_kmeans.py:43-44) of a cluster with count_j > 0:  ch_j' = (float)(sum_i (double)h_i / (double)count_j), cw_j' likewise
+ *   (the order of the double sum is the implementation's: fixed, so the same inputs give the same bits); a cluster with
+ *   count_j == 0 keeps its centroid
+ * yolo_anchor_assign: one assignment pass.  assign (n) and best_iou (n) may be NULL; counts (k); mean_iou (1) =
+ *  sum over valid rows of (double)q_i / n_valid, 0 when n_valid == 0; n_valid (1).
+ * yolo_anchor_kmeans: restart r starts from init[r] (R, k, 2) and repeats assign + update.  It is CONVERGED after the first round whose
+ *  new centroids equal the old ones bit for bit (that round is counted in iters[r]); otherwise it stops after max_iters rounds with
+ *  converged[r] = 0.  centroids (R, k, 2); counts (R, k) and mean_iou (R) are those of one more assignment pass on the RETURNED
+ *  centroids, so they agree with yolo_anchor_assign on them; iters (R), converged (R), n_valid (1).  Restarts are independent: restart
+ *  r of an R-restart call equals, bit for bit, a one-restart call with init[r].  init must be finite and positive; with anything else
+ *  that restart's result is unspecified, but the loop still ends at max_iters and no access leaves the buffers.
+ * One workgroup per restart, no atomics, no communication between workgroups.  workspace: yolo_anchor_workspace_bytes(n, R, k) bytes,
+ * 8-byte aligned, caller-owned (the present decomposition keeps nothing there; the size is small and positive).
+ * YOLO_EINVAL: a NULL pointer other than assign / best_iou, n, k, R or max_iters < 1, stride < 2, a pointer not aligned to its
+ * element (mean_iou and workspace: 8 bytes).  YOLO_EUNSUPPORTED: k > 32 (yolo_grid_desc's 4 scales x 8 anchors), R > 65535,
+ * max_iters > 10000.  Validation comes before any launch.  yolo_anchor_workspace_bytes returns YOLO_EINVAL for a size < 1.
+ * 8-byte row loads when stride == 2 and sizes is 8-byte aligned, scalar ones otherwise. */
+long long yolo_anchor_workspace_bytes(int n, int R, int k);
+int yolo_anchor_assign(const float* sizes, long long stride, int n, const float* centroids, int k, int* assign, float* best_iou,
+                       int* counts, double* mean_iou, int* n_valid, void* workspace, void* stream);
+int yolo_anchor_kmeans(const float* sizes, long long stride, int n, const float* init, int R, int k, int max_iters, float* centroids,
+                       int* counts, double* mean_iou, int* iters, int* converged, int* n_valid, void* workspace, void* stream);
+
 /* 2x nearest up-sample of `up` (N,H/2,W/2,C1) + channel concat with `route` (N,H,W,C2) ->
  * (N,H,W,C1+C2), up-sampled channels first: gluoncv _upsample + F.concat, car/utils.py:92-93. */
 int yolo_upsample2x_concat(const void* up, const void* route, void* y, int N, int H, int W,

@@ -23,4 +23,7 @@ def __getattr__(name):
     if name == 'BackgroundBank':
         from . import background
         return background.BackgroundBank
+    if name in ('fit_anchors', 'sample_sizes', 'anchor_quality', 'AnchorFit'):
+        from . import anchors
+        return getattr(anchors, name)
     raise AttributeError(name)

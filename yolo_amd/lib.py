@@ -87,6 +87,9 @@ SIGNATURES = {
     'yolo_bg_workspace_bytes': (_ll, [_i, _i, _i]),
     'yolo_bg_stats': (_i, [_vp, _ll, _vp, _vp, _i, _i, _i, _vp]),
     'yolo_bg_render': (_i, [_vp, _ll, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'yolo_anchor_workspace_bytes': (_ll, [_i, _i, _i]),
+    'yolo_anchor_assign': (_i, [_vp, _ll, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'yolo_anchor_kmeans': (_i, [_vp, _ll, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'yolo_upsample2x_concat': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'yolo_decode': (_i, [_vp, _vp, _i, _i, C.POINTER(GridDesc), _vp]),
     'yolo_decode_scores': (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(GridDesc), _i, _vp]),
