@@ -223,6 +223,20 @@ int yolo_stem_down_fwd(const float* x_nchw, const float* w1_oihw, const float* s
                        const void* w2_packed, const float* scale2, const float* bias2, void* y, int N, int H, int W,
                        int C1, int C2, int dtype, float slope, void* stream);
 
+/* The first FOUR convolutions fused for inference: yolo_stem_down_fwd followed by yolo_res_block_fwd at C = 64 as ONE kernel
+ * (csrc/stem_res.hip), (N,3,H,W) float32 NCHW image -> y (N,H/2,W/2,C2) NHWC, the output of the first stage's residual block; the
+ * C2-channel map between the down-sampling conv and the block stays in LDS.  w0_oihw (C1,3,3,3) float32; wd / w1 / w2_packed =
+ * yolo_pack_conv_weights images of the (C2,C1,3,3), (C2/2,C2,1,1) and (C2,C2/2,3,3) convs; scale / bias = yolo_fold_bn of each
+ * layer.  Bit-identical to the two calls it replaces.  C1 == 32, C2 == 64, YOLO_BF16 / YOLO_F16, even H and W only
+ * (YOLO_EUNSUPPORTED otherwise, nothing is launched: run the two kernels). */
+int yolo_stem_res_fwd(const float* x_nchw, const float* w0_oihw, const float* scale0, const float* bias0,
+                      const void* wd_packed, const float* scaled, const float* biasd, const void* w1_packed,
+                      const float* scale1, const float* bias1, const void* w2_packed, const float* scale2,
+                      const float* bias2, void* y, int N, int H, int W, int C1, int C2, int dtype, float slope, void* stream);
+/* Its launch geometry for an image shape on the current device (host only): column strips per image, their width in output
+ * columns, output rows per row slice, row slices; the grid is (N * nstrips, slices), sized to one block per compute unit. */
+int yolo_stem_res_geometry(int N, int H, int W, int* nstrips, int* strip_w, int* rows_per_slice, int* slices);
+
 /* Synthetic-target compositing of RenderCar.render (car/render_car.py:135-137): out = clip((bg / 255) * (1 - mask) +
  * fg * mask, 0, 1) over n float32 elements (n % 4 == 0; (B,3,H,W) tensors: bg 0..255, fg and mask 0..1). */
 int yolo_composite(const float* bg, const float* fg, const float* mask, float* out, long long n, void* stream);

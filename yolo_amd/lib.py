@@ -75,6 +75,8 @@ SIGNATURES = {
     'yolo_stem_conv_fwd_stats': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     'yolo_stem_down_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp]),
     'yolo_res_block_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
+    'yolo_stem_res_fwd': (_i, [_vp] * 14 + [_i, _i, _i, _i, _i, _i, _f, _vp]),
+    'yolo_stem_res_geometry': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     'yolo_composite': (_i, [_vp, _vp, _vp, _vp, _ll, _vp]),
     'yolo_composite_unit': (_i, [_vp, _vp, _vp, _vp, _ll, _vp]),
     'yolo_render_workspace_bytes': (_ll, [_i, _i, _i]),

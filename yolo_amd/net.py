@@ -67,6 +67,10 @@ class CarNet(object):
         # fuse_stem: run the stem and the first down-sampling conv as one kernel where yolo_stem_down_fwd takes the
         # shape (32 -> 64, bf16); the stem's own output is then not materialised (no 'stem' parity tap)
         self.fuse_stem = bool(fuse_stem)
+        # ... and, with fuse_res, also the first residual block (yolo_stem_res_fwd: the 64-channel map between the down conv and the
+        # block stays in LDS) where the tuner measured that one launch faster than the two (a 'stem_res' entry of the plan /
+        # tune='measure'; never under tune='auto').  fuse_stem='force': tests -- wherever the kernel takes the shape
+        self._force_stem_res = fuse_stem == 'force'
         # side_stream: a detection block's tip + output convolutions run on a second HIP stream, concurrently with the
         # transition -> up-sample/concat -> first 1x1 chain of the next scale (both only read the block's route): the
         # small kernels of that chain fill the CUs the 13x13 / 26x26 tip kernels leave idle
@@ -325,6 +329,41 @@ class CarNet(object):
         # (default True -- tune='plan', unknown shape: the heuristic's answer, as under tune='auto')
         return self.tuner.fused(('res', shp[0], shp[1], shp[2], C_, dt), True, setup)
 
+    def _use_stem_res(self, stem_payload, c1, c2, shp, H, W):
+        """Whether stem + first down-sampling conv + the first residual block (c1, c2) run as ONE kernel (yolo_stem_res_fwd) instead of
+        yolo_stem_down_fwd followed by yolo_res_block_fwd.  shp: the block's (N, H/2, W/2, 64) map."""
+        if not (self.fuse_stem and self._res_block_eligible(c1, c2)) or shp[3] != 64 or H % 2 or W % 2:
+            return False
+        if self._force_stem_res:
+            return True
+        dt = _LIB_DT[self.dtype]
+
+        def setup():
+            lib, st, tdt = self._lib, L.stream_ptr(), _TORCH_DT[self.dtype]
+            img = torch.rand((shp[0], 3, H, W), dtype=torch.float32, device=self.device)
+            mid = torch.empty(shp, dtype=tdt, device=self.device)
+            out = torch.empty(shp, dtype=tdt, device=self.device)
+            sd = stem_payload[:6] + (L.ptr(mid),) + stem_payload[7:]
+            rb = self._res_block_payload(c1, c2, mid, out, shp)
+            sr = self._stem_res_payload(stem_payload, c1, c2, out)
+
+            def fused(own=(img, out)):
+                return lib.yolo_stem_res_fwd(img.data_ptr(), *sr, dt, LEAKY_SLOPE, st)
+
+            def separate(own=(img, mid, out)):
+                L.check(lib.yolo_stem_down_fwd(img.data_ptr(), *sd, dt, LEAKY_SLOPE, st), 'stem_down')
+                L.check(lib.yolo_res_block_fwd(*rb, dt, LEAKY_SLOPE, st), 'res_block')
+            return fused, separate
+        # (default False: the one launch is only used where a measurement -- the plan's or tune='measure''s -- found it faster)
+        return self.tuner.fused(('stem_res', shp[0], shp[1], shp[2], shp[3], dt), False, setup, windows=3)
+
+    def _stem_res_payload(self, stem_payload, c1, c2, out):
+        """yolo_stem_res_fwd's arguments after the image, from a 'stem_down' payload and the block's two convs."""
+        w0, s0, b0, wpd, sd, bd, _, B, H, W, ch1, ch2 = stem_payload
+        wp1, s1, b1 = self._prepared[c1.name]
+        wp2, s2, b2 = self._prepared[c2.name]
+        return (w0, s0, b0, wpd, sd, bd, L.ptr(wp1), L.ptr(s1), L.ptr(b1), L.ptr(wp2), L.ptr(s2), L.ptr(b2), L.ptr(out), B, H, W, ch1, ch2)
+
     def _separate(self, da, db, own=None):
         """A launch closure: the two convolutions a fused kernel is timed against, one after the other (own: tensors it keeps alive)."""
         lib, st = self._lib, L.stream_ptr()
@@ -419,6 +458,17 @@ class CarNet(object):
             x, shp = self._conv_op(plan, down, x, shp, out=dout, tail=tl)
         for j, (c1, c2) in enumerate(res):
             last = cat_view is not None and j == len(res) - 1
+            sd = plan.ops[-1] if (j == 0 and down_done and plan.ops and plan.ops[-1][0] == 'stem_down') else None
+            if sd is not None and not last and self._use_stem_res(sd[1], c1, c2, shp, sd[1][8], sd[1][9]):
+                # the 'stem_down' launch becomes 'stem_res': its output map is no longer materialised (no stages.0.down tap)
+                out = torch.empty(shp, dtype=tdt, device=self.device)
+                plan.buffers = [b for b in plan.buffers if b is not x]
+                plan.buffers.append(out)
+                plan.act.pop(down.name, None)
+                plan.ops[-1] = ('stem_res', self._stem_res_payload(sd[1], c1, c2, out), c2.name)
+                plan.act[c2.name] = (out, shp)
+                x = out
+                continue
             if not last and pre_mid is None and self._use_res_block(c1, c2, x, shp):
                 out = torch.empty(shp, dtype=tdt, device=self.device)
                 plan.buffers.append(out)
@@ -668,6 +718,8 @@ class CarNet(object):
             return lib.yolo_stem_down_fwd(x.data_ptr(), w1, s1, b1, wp2, s2, b2, y, B, H, W, c1, c2, dt, LEAKY_SLOPE, st)
         if kind == 'res_block':
             return lib.yolo_res_block_fwd(*payload, dt, LEAKY_SLOPE, st)
+        if kind == 'stem_res':
+            return lib.yolo_stem_res_fwd(x.data_ptr(), *payload, dt, LEAKY_SLOPE, st)
         return lib.yolo_upsample2x_concat(*payload, dt, st)
 
     def plan_kernels(self, B, H, W):
@@ -687,6 +739,11 @@ class CarNet(object):
                 c = by_name[name]
                 ho, wo = c.out_hw(H_, W_)
                 out.append((name, 'stem_down_kernel', 2 * 3 * 9 * payload[10] * B_ * H_ * W_ + 2 * c.cin * 9 * c.cout * ho * wo * B_))
+                continue
+            if kind == 'stem_res':                           # (stem, down conv, 1x1 and 3x3 of the block)
+                B_, H_, W_, ch1, ch2 = payload[13:18]
+                px = B_ * (H_ // 2) * (W_ // 2)
+                out.append((name, 'stem_res_kernel', 2 * 3 * 9 * ch1 * B_ * H_ * W_ + 2 * ch1 * 9 * ch2 * px + 2 * px * (ch2 * (ch2 // 2) + 9 * (ch2 // 2) * ch2)))
                 continue
             if kind == 'res_block':
                 N_, H_, W_, C_ = payload[8:12]

@@ -12,7 +12,7 @@ for an algo id or a yes / no.  The rules are plain functions of a timing functio
     Trainer of one net -- net.trainer(size), resized() -- shares the net's Tuner, so a later one finds the earlier ones' choices);
   * data-gradient convs share the forward convs' key space (no slope in the key) and cache: the 'dgrad' entry is a copy of that
     answer; under tune='plan' a missing data-gradient shape is recorded as 0, a missing weight-gradient shape returns 0 unrecorded;
-  * profiles/plan.json is loaded as it is (meta.md5 verified); its 'tail' and 'res' entries are honoured;
+  * profiles/plan.json is loaded as it is (meta.md5 verified); its 'tail', 'res' and 'stem_res' entries are honoured;
   * nothing here touches the library: the same kernels, the same ids.
 """
 import json
@@ -145,7 +145,7 @@ class Tuner(object):
         return best
 
     def fused(self, key, default, setup, windows=1):
-        """Whether the fused kernel of `key` ('res' / 'tail' entries of the 'algo' section) is used; setup() -> (fused, separate) launch closures,
+        """Whether the fused kernel of `key` ('res' / 'tail' / 'stem_res' entries of the 'algo' section) is used; setup() -> (fused, separate) launch closures,
         built only when the pair is timed.  The closures must OWN the memory their launches touch: nothing else setup() made outlives it."""
         if not self.applies:
             return default
