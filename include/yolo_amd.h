@@ -401,6 +401,77 @@ int yolo_anchor_assign(const float* sizes, long long stride, int n, const float*
 int yolo_anchor_kmeans(const float* sizes, long long stride, int n, const float* init, int R, int k, int max_iters, float* centroids,
                        int* counts, double* mean_iou, int* iters, int* converged, int* n_valid, void* workspace, void* stream);
 
+/* Frame overlay: the drawing end of the reference's video node (car/video_node.py:235-326 Video.process / visualize,
+ * car_and_LP/carLP_video_node.py:74-86 visualize_carlp) from rows that are still on the device: the car box of cv2_add_bbox
+ * (yolo_modules/yolo_cv.py:239-270), the plate edges and the clipped plate's map of ProjectRectangle6D.add_edges
+ * (licence_plate_render/__init__.py:379-402), and the NMS boxes (no counterpart in the reference).  Text labels, the radar plot and the
+ * depth lookup are not offered.
+ * The shape table, 16-byte aligned: per image K slots of YOLO_OVERLAY_SLOT_WORDS int32 words
+ *   0..7 the four vertices x0 y0 x1 y1 x2 y2 x3 y3 (frame pixels)   8 colour (4 bytes, byte c = channel c)   9 thickness t   10 enabled
+ *   11 unused
+ * yolo_overlay_table_bytes(B, K) is its size (YOLO_EINVAL for a size < 1, YOLO_EUNSUPPORTED for K > YOLO_OVERLAY_MAX_SLOTS).
+ *
+ * yolo_overlay_shapes fills the table (B, K, 12) and optionally `vertices` (B, K, 4, 2) fp32 (may be NULL), one thread per slot.  The
+ * slots in painter's order (a later slot paints over an earlier one), each source present iff its first pointer is not NULL, and K must
+ * be their sum:
+ *  post_nms NMS slots -- rows (B, nbox, rows_C) [score, l, t, r, b, rot, cls...], kept (B, post_nms), kept_count (B), cand_per_box as
+ *   yolo_decode_nms / yolo_nms_from_scores return them.  Slot j is kept position j: id = kept[b][j]; disabled if j >= min(kept_count[b],
+ *   post_nms), id < 0 or box = id / cand_per_box >= nbox.  Colour = palette[(id % cand_per_box) % npalette] (palette: npalette x 4 bytes
+ *   on the device).  Vertices (l W, t H), (r W, t H), (r W, b H), (l W, b H): no rotation.
+ *  one top-1 slot -- pred (B, pred_C) [score, y, x, h, w, rot, cls...] (yolo_predict_top1): cv2_add_bbox's corners, in its order
+ *   (:259-264), r = use_r ? -rot : 0;  h = pred[3] H;  w = pred[4] W;  s = (pred[2] W, pred[1] H);
+ *   wc = (w cos r) / 2;  hs = (h sin r) / 2;  ws = (w sin r) / 2;  hc = (h cos r) / 2
+ *   v0 = ((wc - hs) + s.x, (ws + hc) + s.y)    v1 = ((-wc - hs) + s.x, (-ws + hc) + s.y)
+ *   v2 = ((-wc + hs) + s.x, (-ws - hc) + s.y)  v3 = ((wc + hs) + s.x, (ws - hc) + s.y)
+ *   enabled iff score > car_threshold (strict, car/video_node.py:316); colour car_color.
+ *  one plate slot -- lp (B, 7) [score, X, Y, Z, r1, r2, r3] (yolo_predict_lp_nhwc), the camera fx, fy, cx, cy, cam_w, cam_h:
+ *   projection_matrix's closed form (:352-377), a = sin r1 cos r2 84, b = sin r1 sin r2 cos r3 84, c = sin r2 199.5, d = sin r3 cos r1 84,
+ *   e = cos r2 cos r3 199.5, f = sin r1 sin r2 sin r3 84, g = sin r3 cos r2 199.5, h = cos r1 cos r3 84 (products left to right), and the
+ *   three rows of `ans` as written there (sums left to right); corner i = (float)(ans[0][i] / ans[2][i]), (float)(ans[1][i] / ans[2][i])
+ *   as __call__ returns it (:344-348), then scaled IN FP32 by xs = (float)((double)W / cam_w), ys = (float)((double)H / cam_h)
+ *   (add_edges :382-386).  Enabled iff score > lp_threshold; colour lp_color.
+ *  Every operation is fp64 (the inputs converted from fp32 first; sin and cos are the device library's) in the written order, nothing
+ *  fused, except the plate's two fp32 steps above.  `vertices` are the fp64 vertices rounded to fp32 (the plate's: the fp32 scaled
+ *  corners).  A vertex becomes an integer by truncation toward zero (numpy's astype(int)); a slot one of whose vertices is not finite or
+ *  has |coordinate| > 2^20 is disabled and its integer vertices are 0.  The thickness of every slot is `thickness`.
+ *  With lp the kernel also writes matrices (B, 9) fp32 -- the map from a pixel of the (lp_h, lp_w) plate image to frame pixels that
+ *  yolo_warp_u8_to_nchw takes (yolo_amd/intake.py plate_matrix on the host) -- and lp_valid (B) bytes.  The eight unknowns m0..m7 of
+ *   u = (m0 x + m1 y + m2) / (m6 x + m7 y + 1),  v = (m3 x + m4 y + m5) / (m6 x + m7 y + 1)   through the four pairs
+ *   (x, y) = (lp_w, lp_h), (0, lp_h), (0, 0), (lp_w, 0) [the reference's order, :392-395]  ->  (u, v) = the fp32 scaled corners, as doubles:
+ *   rows 0..3 = [x, y, 1, 0, 0, 0, -x u, -y u | u], rows 4..7 = [0, 0, 0, x, y, 1, -x v, -y v | v].  Gaussian elimination in fp64: for
+ *   column k = 0..7 the pivot row is the one of rows k..7 with the largest |A[r][k]| (the lowest such row among equals), swapped into
+ *   row k; for r = k+1..7: f = A[r][k] / A[k][k], A[r][c] = A[r][c] - f A[k][c] for c = k..8.  Back-substitution for k = 7..0:
+ *   s = A[k][8]; s = s - A[k][c] m_c for c = k+1..7 in that order; m_k = s / A[k][k].  The matrix is [(float)m0..(float)m7, 1].
+ *   lp_valid = score > lp_threshold, and the four ans[2][i] are non-zero, and the corners are finite, and every pivot is non-zero and
+ *   finite, and m0..m7 are finite.  Otherwise the matrix is [0, 0, -4, 0, 0, -4, 0, 0, 1]: the warp then reads only outside the frame
+ *   and, with border 0, returns zeros.  No NaN is ever written to a matrix.
+ * YOLO_EINVAL: a NULL table, B, H, W, K or thickness < 1, all three sources NULL, K not the sum above, an incomplete source (rows without
+ *  kept / kept_count / palette, nbox, post_nms, cand_per_box or npalette < 1, rows_C < 5, pred_C < 6, lp without matrices / lp_valid or
+ *  with a non-positive camera or plate size), a table not 16-byte aligned, a vertices / matrices pointer not 4-byte aligned.  YOLO_EUNSUPPORTED:
+ *  K > YOLO_OVERLAY_MAX_SLOTS, H or W > 16384, thickness > 255.
+ *
+ * yolo_overlay_draw paints a table (N, K, 12) onto frames (N, H, W, C) uint8 in place, C in 1..4, frames at ANY byte address.  This is
+ * a definition of its own, not cv2.polylines' pixels (a Bresenham line thickened to 2 px; this rule gives 3 px on an axis-aligned edge
+ * at t = 2).  Shape s paints pixel P = (x, y) iff for one of its four closed segments A -> B (vertices 0-1, 1-2, 2-3, 3-0) the distance
+ * from the integer point to the segment satisfies 4 dist^2 <= t^2, decided exactly in integers: d = B - A, p = P - A, u = p . d;
+ *   u <= 0: 4 |p|^2 <= t^2;    u >= d . d: 4 |p - d|^2 <= t^2;    otherwise: 4 cross(p, d)^2 <= t^2 (d . d)
+ * (A = B is the first case: a disc).  The pixel takes bytes 0..C-1 of the colour of the HIGHEST enabled slot that paints it; a pixel no
+ * enabled slot paints is not written, and the frame of an image without an enabled slot is not accessed at all.  A slot counts as
+ * enabled iff word 10 != 0, 1 <= t <= 255 and every vertex coordinate lies in [-2^20, 2^20]; with those limits and H, W <= 16384 no
+ * intermediate leaves 64 bits (|cross| >= 2^31 is already outside).  No frame byte is read; no atomics and no dependence on block
+ * order: the result is bitwise reproducible.
+ * YOLO_EINVAL: a NULL pointer, N, H, W, C or K < 1, a table not 16-byte aligned.  YOLO_EUNSUPPORTED: K > YOLO_OVERLAY_MAX_SLOTS, C > 4,
+ *  H or W > 16384.  Validation comes before any launch. */
+#define YOLO_OVERLAY_SLOT_WORDS 12
+#define YOLO_OVERLAY_MAX_SLOTS 128
+long long yolo_overlay_table_bytes(int B, int K);
+int yolo_overlay_shapes(const float* rows, const int* kept, const int* kept_count, int nbox, int rows_C, int post_nms, int cand_per_box,
+                        const unsigned char* palette, int npalette, const float* pred, int pred_C, float car_threshold, int use_r,
+                        unsigned car_color, const float* lp, double fx, double fy, double cx, double cy, int cam_w, int cam_h,
+                        float lp_threshold, unsigned lp_color, int lp_h, int lp_w, int B, int H, int W, int thickness, int* table, int K,
+                        float* vertices, float* matrices, unsigned char* lp_valid, void* stream);
+int yolo_overlay_draw(unsigned char* frames, const int* table, int N, int H, int W, int C, int K, void* stream);
+
 /* 2x nearest up-sample of `up` (N,H/2,W/2,C1) + channel concat with `route` (N,H,W,C2) ->
  * (N,H,W,C1+C2), up-sampled channels first: gluoncv _upsample + F.concat, car/utils.py:92-93. */
 int yolo_upsample2x_concat(const void* up, const void* route, void* y, int N, int H, int W,

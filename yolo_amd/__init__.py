@@ -8,7 +8,7 @@ def __getattr__(name):
     if name in ('CarNet', 'CarLPNet'):
         from . import net
         return getattr(net, name)
-    if name in ('Detector', 'get_iou', 'cv_img_2_ndarray', 'make_grid', 'predict_LP', 'predict_LP_batch', 'default_ltrb'):
+    if name in ('Detector', 'get_iou', 'cv_img_2_ndarray', 'make_grid', 'predict_LP', 'predict_LP_batch', 'predict_LP_rows', 'default_ltrb'):
         from . import detect
         return getattr(detect, name)
     if name == 'Evaluator':
@@ -23,6 +23,9 @@ def __getattr__(name):
     if name == 'BackgroundBank':
         from . import background
         return background.BackgroundBank
+    if name == 'FrameOverlay':
+        from . import overlay
+        return overlay.FrameOverlay
     if name in ('fit_anchors', 'sample_sizes', 'anchor_quality', 'AnchorFit'):
         from . import anchors
         return getattr(anchors, name)

@@ -125,7 +125,10 @@ class FrameIntake(object):
     non-blocking copy, a pinned tensor is copied from where it is, a device tensor is read in place.  The matrix is cached
     per source size, the buffers per (batch, source size): once a batch size has been seen a call allocates nothing -- the
     returned tensor is THE OBJECT'S buffer for that batch size and is overwritten by the next call with it (pass out= to
-    keep results apart).  Runs on the current stream and does not synchronise."""
+    keep results apart).  Runs on the current stream and does not synchronise.
+    `frames` is the device uint8 (N,H,W,C) batch the last call read -- the uploaded staging buffer (overwritten by the next upload of
+    that shape) or the caller's own tensor --, what FrameOverlay draws on; None before the first call.  The caller's tensor is held
+    WEAKLY (the intake does not extend its life): None once the caller has dropped it."""
 
     def __init__(self, size, device='cuda:0', clip=(1., 1.), flip=None, white_balance=None):
         import torch
@@ -143,6 +146,15 @@ class FrameIntake(object):
         self._mat = {}                    # (N, H, W) -> device (N,9) matrix
         self._stage = {}                  # (N, H, W, C) -> [pinned host buffer, device buffer, event of the last upload]
         self._out = {}                    # (N, C) -> device output
+        self._read = None                 # the staging buffer of the last call, or a weak reference to the caller's device tensor
+
+    @property
+    def frames(self):
+        import weakref
+        if isinstance(self._read, weakref.ref):
+            t = self._read()
+            return None if t is None else _as_u8_batch(t)
+        return self._read
 
     def matrix(self, src_hw):
         """(M float64 (3,3), roi) for frames of src_hw: intake_matrix with this object's size, clip and flip."""
@@ -180,7 +192,9 @@ class FrameIntake(object):
 
     def __call__(self, frames, out=None):
         import torch
+        import weakref
         L.require_current_device(self.device, 'this FrameIntake')
+        given = frames
         frames = _as_u8_batch(frames)
         if frames.shape[3] != 3 and self._gain is not None:
             raise ValueError('white_balance needs 3-channel frames')
@@ -199,6 +213,7 @@ class FrameIntake(object):
         elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
             raise ValueError('out should be a contiguous float32 tensor of shape %r on %s' % (shape, self.device))
         _launch(frames, M, out, BORDERS['replicate'], roi, self._gain)
+        self._read = weakref.ref(given) if (torch.is_tensor(given) and given.is_cuda) else frames
         return out
 
 

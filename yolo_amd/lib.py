@@ -56,7 +56,7 @@ class GridDesc(C.Structure):
 
 
 # name -> (restype, argtypes); must list every symbol include/yolo_amd.h declares
-_vp, _i, _f, _ll = C.c_void_p, C.c_int, C.c_float, C.c_longlong
+_vp, _i, _f, _ll, _d, _u = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_double, C.c_uint
 SIGNATURES = {
     'yolo_version': (_i, []),
     'yolo_packed_weight_bytes': (_ll, [_i, _i, _i, _i]),
@@ -92,6 +92,10 @@ SIGNATURES = {
     'yolo_anchor_workspace_bytes': (_ll, [_i, _i, _i]),
     'yolo_anchor_assign': (_i, [_vp, _ll, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'yolo_anchor_kmeans': (_i, [_vp, _ll, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'yolo_overlay_table_bytes': (_ll, [_i, _i]),
+    'yolo_overlay_shapes': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _i, _u, _vp, _d, _d, _d, _d, _i, _i, _f, _u, _i, _i,
+                                 _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    'yolo_overlay_draw': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'yolo_upsample2x_concat': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'yolo_decode': (_i, [_vp, _vp, _i, _i, C.POINTER(GridDesc), _vp]),
     'yolo_decode_scores': (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(GridDesc), _i, _vp]),
