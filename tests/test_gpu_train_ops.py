@@ -9,7 +9,8 @@ import torch
 import torch.nn.functional as F
 
 from yolo_amd import lib as L
-from util import to_nhwc, from_nhwc
+from util import to_nhwc, from_nhwc, guarded, guards_intact, moated, eligible_pairs
+from test_gpu_conv import PIPE_ALGOS
 
 pytestmark = pytest.mark.gpu
 
@@ -66,6 +67,121 @@ def test_dgrad(lib, cuda, case):
     d.residual = out.data_ptr()
     assert lib.yolo_conv_fwd(C.byref(d), st) == 0
     np.testing.assert_allclose(from_nhwc(out), 2 * dx_ref, rtol=1e-3, atol=2e-3 * np.abs(dx_ref).max())
+
+
+# forward convs (N, Cin_f, H, W, Cout_f, k) whose stride-1 data gradient test_dgrad_bf16_variants runs
+DGRAD_BF16 = [(2, 40, 9, 11, 72, 3), (2, 64, 13, 13, 32, 1), (2, 32, 13, 13, 64, 3), (1, 128, 13, 13, 256, 3), (3, 256, 13, 13, 128, 1),
+              (5, 16, 3, 5, 24, 3)]
+# the output conv as Trainer._dgrad runs it: Cout_f = 90, k = 1, Cin_f = 128, gradient rows padded to 96 channels
+DGRAD_HEAD = (2, 128, 13, 13, 90, 1)
+HEAD_PAD = 96
+DGRAD_ALGOS = [0, 1, 13, 14] + PIPE_ALGOS
+
+
+def _dgrad_desc_case(fwd, cin=None):
+    """The conv case (N, Cin, H, W, Cout, k, stride) of the data gradient of forward conv `fwd`: channels swapped, stride 1."""
+    N, Cin_f, H, W, Cout_f, k = fwd
+    return (N, cin or Cout_f, H, W, Cin_f, k, 1)
+
+
+_DGRAD_PAIRS = [pytest.param(fwd, HEAD_PAD if fwd is DGRAD_HEAD else None, p.values[2], id=('head-' if fwd is DGRAD_HEAD else '') + p.id)
+                for fwd in DGRAD_BF16 + [DGRAD_HEAD]
+                for p in eligible_pairs([_dgrad_desc_case(fwd, HEAD_PAD if fwd is DGRAD_HEAD else None)], ['bf16'], DGRAD_ALGOS)]
+
+
+@pytest.mark.parametrize('fwd,pad_to,algo', _DGRAD_PAIRS)
+def test_dgrad_bf16_variants(lib, cuda, fwd, pad_to, algo):
+    """The stride-1 data gradient in bf16 -- yolo_pack_conv_weights_dgrad's image run by yolo_conv_fwd with the identity epilogue
+    (scale = bias = NULL) -- by every tile variant that takes the shape, fresh and accumulating in place (residual = y), against
+    float64 autograd on the bf16-rounded w and dy.  Bar per element: 2**-7 |ref| (one bf16 unit of the stored value: a value within
+    fp32 noise of a rounding boundary may fall either way) + 1e-3 max|ref| (the fp32 accumulation allowance of test_dgrad);
+    accumulating doubles both terms.  Operands in moats, the gradient between guard bands."""
+    N, Cin_f, H, W, Cout_f, k = fwd
+    rng = np.random.default_rng(17)
+    rb = lambda a: torch.from_numpy(a).to(torch.bfloat16)
+    w = (rng.standard_normal((Cout_f, Cin_f, k, k)) / np.sqrt(Cin_f * k * k)).astype(np.float32)
+    dy = rng.standard_normal((N, Cout_f, H, W)).astype(np.float32)
+    xz = torch.zeros((N, Cin_f, H, W), dtype=torch.float64, requires_grad=True)
+    F.conv2d(xz, rb(w).double(), None, stride=1, padding=k // 2).backward(rb(dy).double())
+    ref = xz.grad.numpy()
+    st = torch.cuda.current_stream().cuda_stream
+    cin = pad_to or Cout_f                                         # channels of a gradient row (the head's: zero padded)
+    wbuf, wd = guarded((lib.yolo_packed_weight_bytes(Cin_f, Cout_f, k, L.BF16),), torch.uint8, cuda)
+    assert lib.yolo_pack_conv_weights_dgrad(moated(torch.from_numpy(w).to(cuda)).data_ptr(), wd.data_ptr(), Cout_f, Cin_f, k, L.BF16, st) == 0
+    rows = torch.zeros((N, H, W, cin), dtype=torch.bfloat16, device=cuda)
+    rows[..., :Cout_f] = to_nhwc(dy, 'bf16', cuda)
+    dyd = moated(rows)
+    obuf, out = guarded((N, H, W, Cin_f), torch.bfloat16, cuda)
+    d = L.ConvDesc()
+    d.x, d.w_packed, d.y = dyd.data_ptr(), wd.data_ptr(), out.data_ptr()
+    d.N, d.H, d.W, d.Cin, d.Cout, d.ksize, d.stride, d.dtype, d.slope, d.algo = N, H, W, cin, Cin_f, k, 1, L.BF16, 1.0, algo
+    assert lib.yolo_conv_fwd(C.byref(d), st) == 0
+    torch.cuda.synchronize()
+    guards_intact(wbuf, wd)
+    guards_intact(obuf, out)
+    bar = 2.0 ** -7 * np.abs(ref) + 1e-3 * np.abs(ref).max()
+    got = from_nhwc(out).astype(np.float64)
+    assert np.isfinite(got).all()
+    err = np.abs(got - ref)
+    print('fresh: max err / bar = %.3f' % float((err / bar).max()))
+    assert (err <= bar).all(), 'fresh: %d elements beyond the bar, worst %.3f of it' % (int((err > bar).sum()), float((err / bar).max()))
+    d.residual = out.data_ptr()                                    # accumulate into the existing gradient, in place
+    assert lib.yolo_conv_fwd(C.byref(d), st) == 0
+    torch.cuda.synchronize()
+    guards_intact(obuf, out)
+    got = from_nhwc(out).astype(np.float64)
+    assert np.isfinite(got).all()
+    err = np.abs(got - 2 * ref)
+    print('accumulating: max err / bar = %.3f' % float((err / (2 * bar)).max()))
+    assert (err <= 2 * bar).all(), 'accumulating: %d elements beyond the bar, worst %.3f of it' % (int((err > 2 * bar).sum()),
+                                                                                                 float((err / (2 * bar)).max()))
+
+
+def test_pack_batch_is_the_single_packers_image(lib, cuda):
+    """yolo_pack_conv_weights_batch -- every fp32 layer and the bf16 stem, head and stride-2 images of each training step -- in ONE
+    launch per element type over records with dgrad 0, 1 and 2: each image, between guard bands and pre-filled with 0xFF, equals
+    byte for byte over its whole yolo_packed_weight_bytes() extent what yolo_pack_conv_weights / _dgrad / _dgrad_s2 write into a
+    buffer pre-filled the same way."""
+    rng = np.random.default_rng(23)
+    st = torch.cuda.current_stream().cuda_stream
+    item_dt = np.dtype([('w', '<u8'), ('packed', '<u8'), ('cout', '<i4'), ('cin', '<i4'), ('k', '<i4'), ('dgrad', '<i4')])
+    convs = [(co, ci, k) for _, ci, _, _, co, k in DGRAD_BF16 + [DGRAD_HEAD]]
+    for ldt in (L.F32, L.BF16):
+        # (record, the single call that writes the same image): forward and data-gradient image of every conv, ...
+        plan = []
+        for co, ci, k in convs:
+            plan.append(((co, ci, k, 0), lambda w, p, co=co, ci=ci, k=k: lib.yolo_pack_conv_weights(w, p, co, ci, k, ldt, st)))
+            plan.append(((ci, co, k, 1), lambda w, p, co=co, ci=ci, k=k: lib.yolo_pack_conv_weights_dgrad(w, p, co, ci, k, ldt, st)))
+        # ... the 3-channel stem (forward only: it receives no gradient), a 3x3 stride-2 conv with its sub-pixel image (bf16 only)
+        plan.append(((32, 3, 3, 0), lambda w, p: lib.yolo_pack_conv_weights(w, p, 32, 3, 3, ldt, st)))
+        plan.append(((64, 32, 3, 0), lambda w, p: lib.yolo_pack_conv_weights(w, p, 64, 32, 3, ldt, st)))
+        plan.append(((32, 64, 3, 1), lambda w, p: lib.yolo_pack_conv_weights_dgrad(w, p, 64, 32, 3, ldt, st)))
+        if ldt == L.BF16:
+            plan.append(((4 * 32, 64, 2, 2), lambda w, p: lib.yolo_pack_conv_weights_dgrad_s2(w, p, 64, 32, ldt, st)))
+        recs, first, keep = [], [0], []
+        for (co, ci, k, dg), single in plan:
+            wshape = {0: (co, ci, k, k), 1: (ci, co, k, k), 2: (ci, co // 4, 3, 3)}[dg]         # the FORWARD conv's weights
+            w = moated(torch.from_numpy(rng.standard_normal(wshape).astype(np.float32)).to(cuda))
+            nbytes = lib.yolo_packed_weight_bytes(co, ci, k, ldt)
+            assert nbytes > 0
+            bbuf, bimg = guarded((nbytes,), torch.uint8, cuda)
+            sbuf, simg = guarded((nbytes,), torch.uint8, cuda)
+            assert single(w.data_ptr(), simg.data_ptr()) == 0, (co, ci, k, dg)
+            nb = lib.yolo_pack_batch_blocks(co, ci, k, ldt)
+            assert nb > 0, (co, ci, k, dg)
+            recs.append((w.data_ptr(), bimg.data_ptr(), co, ci, k, dg))
+            first.append(first[-1] + nb)
+            keep.append((w, bbuf, bimg, sbuf, simg))
+        items = moated(torch.from_numpy(np.array(recs, dtype=item_dt).view(np.uint8).copy()).to(cuda))
+        fb = moated(torch.tensor(first, dtype=torch.int64, device=cuda))
+        assert lib.yolo_pack_conv_weights_batch(items.data_ptr(), fb.data_ptr(), len(recs), first[-1], ldt, st) == 0
+        torch.cuda.synchronize()
+        for ((co, ci, k, dg), _), (w, bbuf, bimg, sbuf, simg) in zip(plan, keep):
+            guards_intact(bbuf, bimg)
+            guards_intact(sbuf, simg)
+            assert torch.equal(bimg, simg), ('f32' if ldt == L.F32 else 'bf16', co, ci, k, dg,
+                                             '%d bytes differ' % int((bimg != simg).sum()))
+            assert not bool((simg == 0xFF).all())                  # (the single call wrote an image)
 
 
 @pytest.mark.parametrize('shape', [(2, 8, 12, 128), (3, 13, 13, 64), (1, 4, 6, 32), (4, 32, 48, 16), (2, 5, 7, 2048 + 64),

@@ -18,6 +18,47 @@ def split_planes(t, rdt=torch.bfloat16):
     return hi, (t - hi.float()).to(rdt)
 
 
+# ---- guard bands and moats: the large kernels address through maximum-range buffer resources, so nothing but their own offset
+# arithmetic keeps them inside a tensor.  0xFF in every byte is a NaN in f32 / bf16 / f16 and -1 in the integer types: one pattern
+# is the poison around an operand (whatever is read beyond it is NaN) and the sentinel around an output (a changed byte was written).
+GUARD_BYTES = 1 << 20          # the largest tile a variant stores: 512 pixels x 256 couts x 4 B (fp32 logits) = 512 KiB
+
+
+def guarded(shape, tdt, dev, prior=None):
+    """-> (buf, view): `view` has `shape` / `tdt` and lies in the flat uint8 `buf`, GUARD_BYTES of 0xFF before and after it and 0xFF
+    in its own bytes (or the contents of `prior`); it starts at a multiple of 512 bytes of `buf` and of the address space."""
+    shape = tuple(int(v) for v in shape)
+    nbytes = int(np.prod(shape, dtype=np.int64)) * torch.empty((), dtype=tdt).element_size()
+    total = 2 * GUARD_BYTES + nbytes
+    raw = torch.full((total + 512,), 0xFF, dtype=torch.uint8, device=dev)
+    lead = -raw.data_ptr() % 512
+    buf = raw[lead:lead + total]
+    view = buf[GUARD_BYTES:GUARD_BYTES + nbytes].view(tdt).view(shape)
+    if prior is not None:
+        view.copy_(prior)
+    return buf, view
+
+
+def guards_intact(buf, view):
+    """Both guards of a guarded() pair still hold 0xFF in every byte; otherwise names the first changed byte by its offset from the
+    view's first byte (negative: before the view; >= the view's size: behind it)."""
+    off = view.storage_offset() * view.element_size() - buf.storage_offset()            # (data_ptr() of an empty view is 0)
+    nbytes = view.numel() * view.element_size()
+    assert (view.untyped_storage().data_ptr() == buf.untyped_storage().data_ptr() and view.is_contiguous() and off == GUARD_BYTES
+            and buf.numel() == 2 * GUARD_BYTES + nbytes), 'not a guarded() pair'
+    for side, g, base in (('before', buf[:off], -off), ('behind', buf[off + nbytes:], nbytes)):
+        if not bool((g == 0xFF).all()):
+            first = int((g != 0xFF).nonzero()[0])
+            raise AssertionError('guard %s the %d-byte view was written: first changed byte at offset %d from the view (%d changed)'
+                                 % (side, nbytes, base + first, int((g != 0xFF).sum())))
+    return True
+
+
+def moated(t):
+    """A copy of operand `t` with GUARD_BYTES of NaN on either side: whatever a kernel reads outside the operand is NaN."""
+    return guarded(t.shape, t.dtype, t.device, prior=t)[1]
+
+
 KERNEL_SETS = ('measured', 'plan')
 
 
@@ -77,18 +118,20 @@ def run_conv(lib, dev, x, w, scale, bias, stride, slope, dtype, residual=None, o
     Cout, _, k, _ = w.shape
     st = torch.cuda.current_stream().cuda_stream
     dt = LDT[dtype]
-    xd = to_nhwc(x, dtype, dev)
-    wd = torch.from_numpy(w).to(dev)
-    wp = torch.empty(lib.yolo_packed_weight_bytes(Cout, Cin, k, dt), dtype=torch.uint8, device=dev)
+    # every operand in a moat of NaN, the packed image and y between guard bands (guarded / moated above)
+    xd = moated(to_nhwc(x, dtype, dev))
+    wd = moated(torch.from_numpy(w).to(dev))
+    wbuf, wp = guarded((lib.yolo_packed_weight_bytes(Cout, Cin, k, dt),), torch.uint8, dev)
     L.check(lib.yolo_pack_conv_weights(wd.data_ptr(), wp.data_ptr(), Cout, Cin, k, dt, st), 'pack')
     cp = lib.yolo_padded_channels(Cout)
     sc = torch.zeros(cp, device=dev); sc[:Cout] = torch.from_numpy(scale).to(dev)
     bi = torch.zeros(cp, device=dev); bi[:Cout] = torch.from_numpy(bias).to(dev)
+    sc, bi = moated(sc), moated(bi)
     pad = k // 2
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     yshape = (N, Ho, Wo, 2, -(-Cout // 32) * 32) if (dtype in SPLIT and not out_f32) else (N, Ho, Wo, Cout)
-    y = torch.full(yshape, float('nan'), dtype=torch.float32 if out_f32 else TDT[dtype], device=dev)
-    rd = to_nhwc(residual, dtype, dev) if residual is not None else None
+    ybuf, y = guarded(yshape, torch.float32 if out_f32 else TDT[dtype], dev)               # (0xFF bytes: y starts as NaN)
+    rd = moated(to_nhwc(residual, dtype, dev)) if residual is not None else None
     d = L.ConvDesc()
     d.x, d.w_packed, d.scale, d.bias = xd.data_ptr(), wp.data_ptr(), sc.data_ptr(), bi.data_ptr()
     d.residual = rd.data_ptr() if rd is not None else None
@@ -102,6 +145,8 @@ def run_conv(lib, dev, x, w, scale, bias, stride, slope, dtype, residual=None, o
     else:
         assert rc == expect_rc, 'yolo_conv_fwd rc=%d' % rc
     torch.cuda.synchronize()
+    guards_intact(wbuf, wp)
+    guards_intact(ybuf, y)
     if y.dim() == 5 and y.shape[-1] != Cout:
         assert bool(torch.isnan(y[..., Cout:]).all()), 'the pad channels of a split plane were written'
         y = y[..., :Cout]
