@@ -404,8 +404,8 @@ int yolo_anchor_kmeans(const float* sizes, long long stride, int n, const float*
 /* Frame overlay: the drawing end of the reference's video node (car/video_node.py:235-326 Video.process / visualize,
  * car_and_LP/carLP_video_node.py:74-86 visualize_carlp) from rows that are still on the device: the car box of cv2_add_bbox
  * (yolo_modules/yolo_cv.py:239-270), the plate edges and the clipped plate's map of ProjectRectangle6D.add_edges
- * (licence_plate_render/__init__.py:379-402), and the NMS boxes (no counterpart in the reference).  Text labels, the radar plot and the
- * depth lookup are not offered.
+ * (licence_plate_render/__init__.py:379-402), and the NMS boxes (no counterpart in the reference).  Text labels: yolo_overlay_labels
+ * and yolo_overlay_text below; the azimuth and the depth lookup of Video.process: yolo_pose_top1.  The radar plot is not offered.
  * The shape table, 16-byte aligned: per image K slots of YOLO_OVERLAY_SLOT_WORDS int32 words
  *   0..7 the four vertices x0 y0 x1 y1 x2 y2 x3 y3 (frame pixels)   8 colour (4 bytes, byte c = channel c)   9 thickness t   10 enabled
  *   11 unused
@@ -471,6 +471,66 @@ int yolo_overlay_shapes(const float* rows, const int* kept, const int* kept_coun
                         float lp_threshold, unsigned lp_color, int lp_h, int lp_w, int B, int H, int W, int thickness, int* table, int K,
                         float* vertices, float* matrices, unsigned char* lp_valid, void* stream);
 int yolo_overlay_draw(unsigned char* frames, const int* table, int N, int H, int W, int C, int K, void* stream);
+
+/* Text labels on the overlay: what cv2_add_bbox_text (yolo_modules/yolo_cv.py:273-282) is for -- class, score and azimuth at a box's
+ * top-left corner.  The reference never calls that helper, so the text is this library's own definition (a bitmap font the caller
+ * brings, an exact integer rule), not cv2.putText's Hershey pixels.
+ * The label table, 16-byte aligned: per image K labels of YOLO_OVERLAY_LABEL_WORDS int32 words, label k belonging to slot k
+ *   0 x   1 y (the top-left pixel of the first character cell; may be negative)   2 text colour   3 ground colour (4 bytes each, byte c =
+ *   channel c)   4 flags (bit 0 enabled, bit 1 ground box on)   5 nchar, 0..YOLO_OVERLAY_LABEL_CHARS
+ *   6..15 the text: byte i in word 6 + i / 4 at bits 8 (i % 4)
+ *
+ * yolo_overlay_labels writes the label table (B, K, 16) for a shape table (B, K, 12) that yolo_overlay_shapes has filled, from the same
+ * sources in the same slot order (rows / kept / kept_count / nbox / rows_C / post_nms / cand_per_box, pred / pred_C, lp: as there; each
+ * present iff its first pointer is not NULL, K their sum), one thread per slot.  A label is enabled iff its slot's word 10 is non-zero
+ * (and, for an NMS slot, its id passes yolo_overlay_shapes' test again: no row is read through an id refused there); a disabled
+ * label is sixteen zero words.  Text colour = the slot's colour word, ground colour = ground_colour, flags = 1 | (ground ? 2 : 0).
+ *  Text = [name ' '] score [' ' deg]:
+ *   name   names[c] up to its first zero byte, at most YOLO_OVERLAY_NAME_BYTES (names: nname x 16 bytes, zero padded, on the device;
+ *          may be NULL with nname 0); left out with its space when c < 0, c >= nname or the name is empty
+ *   score  five bytes.  For a finite s >= 0: n = min(llrint((double)s * 1000.0), 9999) [round to nearest, ties to even] printed as
+ *          d.ddd -- (double)s * 1000.0 is exact, so this is C's "%.3f" digit for digit up to 9.999; otherwise the bytes "-.---"
+ *   deg    d = rint((double)azimuth * 57.29577951308232) printed as an optional '-' and 1..3 digits without padding (-0 prints "0");
+ *          only for the top-1 slot, only with pose and show_deg != 0, only for a finite azimuth with |d| <= 999
+ *  per source:
+ *   NMS slot j   id = kept[b][j];  c = cand_per_box > 1 ? id % cand_per_box : -1;
+ *                s = kept_scores ? kept_scores[b][j] : rows[b][id / cand_per_box][0]   (kept_scores (B, post_nms) may be NULL)
+ *   top-1 slot   s = pred[b][0];  with pose (B, 4) [azimuth, radius, depth, class] of yolo_pose_top1 (may be NULL, else 16-byte aligned):
+ *                c = (int)pose[b][3] when -1 < pose[b][3] < nname, else no name; azimuth = pose[b][0].  Without pose: no name, no deg
+ *   plate slot   s = lp[b][0], no name
+ *  Geometry, integers only (64-bit, x and y saturated to [-2^30, 2^30] at the end): bx0 / by0 = the smallest x / y of the slot's four
+ *  integer vertices (for an unrotated box cv2_add_bbox_text's (left, top));  Th = cell_h scale;  Tw = ((nchar - 1) advance + cell_w) scale
+ *   y = by0 - gap - Th;  if y - pad < 0: y = by0 + gap          (no room above: the label moves under the box's top edge)
+ *   x = bx0;  if x + Tw + pad > W: x = W - Tw - pad;  after that, if x - pad < 0: x = pad
+ * YOLO_EINVAL: a NULL table or labels, B, H, W or K < 1, all three sources NULL, K not their sum, an incomplete source (rows without kept
+ *  / kept_count, nbox, post_nms or cand_per_box < 1, rows_C < 5, pred_C < 6), nname < 0 or names NULL with nname > 0, cell_w, cell_h or
+ *  scale < 1, advance < cell_w, gap or pad < 0, ground not 0 / 1, a table, labels or pose pointer not 16-byte aligned.
+ *  YOLO_EUNSUPPORTED: K > YOLO_OVERLAY_MAX_SLOTS, cell_w or cell_h > 32, scale > 16, H or W > 16384.  Validation comes before any launch.
+ *
+ * yolo_overlay_text paints a label table (N, K, 16) onto frames (N, H, W, C) uint8 in place, C in 1..4, frames at ANY byte address.
+ * font is (nglyph, cell_h) uint32 on the device: bit c of font[g][r] (bit 0 = the leftmost column) is the ink of column c, row r of glyph
+ * g; glyph g draws the byte first_code + g.  With Th and Tw as above:
+ *   character i of a label occupies the cell with origin (ox_i, y) = (x + i advance scale, y) and size (cell_w scale, cell_h scale)
+ *   pixel P is INK of the label iff P lies in the cell of some i < nchar with g = byte_i - first_code in [0, nglyph) and bit
+ *     (Px - ox_i) / scale of font[g][(Py - y) / scale] is set (cells never overlap: advance >= cell_w); a byte outside the font inks nothing
+ *   pixel P is GROUND of the label iff bit 1 of its flags is set, nchar > 0 and P lies in [x - pad, x + Tw + pad) x [y - pad, y + Th + pad)
+ * A pixel inside the frame takes bytes 0..C-1 of the colour of the HIGHEST enabled label of which it is ink or ground -- the text colour
+ * for ink, the ground colour for ground that is not ink; a pixel no label paints is not written, no frame byte is read, and the frame
+ * of an image without an enabled label is not accessed at all.  A label counts as enabled iff bit 0 of its flags is set,
+ * 0 <= nchar <= YOLO_OVERLAY_LABEL_CHARS and |x|, |y| <= 2^20.  No atomics and no dependence on block order: the result is bitwise
+ * reproducible; no store leaves the frame whatever a label holds.
+ * YOLO_EINVAL: a NULL pointer, N, H, W, C, K, nglyph, cell_w, cell_h or scale < 1, advance < cell_w, pad < 0, labels not 16-byte aligned,
+ *  font not 4-byte aligned.  YOLO_EUNSUPPORTED: K > YOLO_OVERLAY_MAX_SLOTS, C > 4, H or W > 16384, cell_w or cell_h > 32, scale > 16,
+ *  nglyph > 256.  Validation comes before any launch. */
+#define YOLO_OVERLAY_LABEL_WORDS 16
+#define YOLO_OVERLAY_LABEL_CHARS 40
+#define YOLO_OVERLAY_NAME_BYTES 16
+int yolo_overlay_labels(const int* table, const float* rows, const int* kept, const int* kept_count, const float* kept_scores, int nbox,
+                        int rows_C, int post_nms, int cand_per_box, const float* pred, int pred_C, const float* pose, int show_deg,
+                        const float* lp, const unsigned char* names, int nname, int cell_w, int cell_h, int advance, int scale, int gap,
+                        int pad, int ground, unsigned ground_colour, int B, int H, int W, int K, int* labels, void* stream);
+int yolo_overlay_text(unsigned char* frames, const int* labels, const unsigned* font, int nglyph, int first_code, int cell_w, int cell_h,
+                      int advance, int scale, int pad, int N, int H, int W, int C, int K, void* stream);
 
 /* 2x nearest up-sample of `up` (N,H/2,W/2,C1) + channel concat with `route` (N,H,W,C2) ->
  * (N,H,W,C1+C2), up-sampled channels first: gluoncv _upsample + F.concat, car/utils.py:92-93. */
@@ -579,6 +639,22 @@ int yolo_eval_match(const float* rows, const int* kept, const int* kept_count, c
  * (an image without an object is marked invalid; the reference scores it against a box of -1s). */
 int yolo_eval_top1(const float* pred, const float* labels, const float* class_dirs, float* out, int B, int C, int nobj,
                    int label_cols, void* stream);
+
+/* The row Video.process publishes (car/video_node.py:235-255, car_and_LP/carLP_video_node.py:48-72), made where the top-1 row is:
+ * pred (B, C) = yolo_predict_top1's rows, C > 6; class_dirs (C - 6, 2) [cos, sin] as above.  pose (B, 4), 16-byte aligned:
+ *   [azimuth (rad), radius, depth, class]
+ *  azimuth, radius  yolo_eval_top1's, by the same device function: the same bits for the same row
+ *  class            (float) of the index of the largest class logit, the lowest index among equals; a NaN never wins (all NaN: 0)
+ *  depth            depth is NULL or (B, Hd, Wd) float32, one depth frame per image.  NULL: -1 (:243).  Otherwise
+ *                   xi = (int)((double)Wd * (double)pred[2]), yi = (int)((double)Hd * (double)pred[1]), truncated toward zero (:239-240),
+ *                   and depth[b][yi][xi] copied as it is, a NaN included.  DEVIATION: -1 when pred[1] or pred[2] is not finite or xi is
+ *                   outside [0, Wd) or yi outside [0, Hd) -- numpy raises there, or wraps a negative index.
+ * rows_out is NULL or (B, C), and may be pred itself: a copy of the row with column 5 left alone (row5 == 0), set to the azimuth
+ * (row5 == 1, :251) or to the depth (row5 == 2, carLP_video_node.py:52-57).  One thread per image; it reads its row before it writes it.
+ * YOLO_EINVAL: a NULL pred, class_dirs or pose, B < 1, C <= 6, depth with Hd or Wd < 1, row5 outside 0..2, pose not 16-byte aligned.
+ * Validation comes before any launch. */
+int yolo_pose_top1(const float* pred, int B, int C, const float* class_dirs, const float* depth, int Hd, int Wd, int row5,
+                   float* rows_out, float* pose, void* stream);
 
 /* ---- training step (fp32 parity path) ------------------------------------------------------- */
 

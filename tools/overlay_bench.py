@@ -6,14 +6,17 @@
            SAME run, alternating with the draw kernel, a device-to-device copy of the same frame batch (torch's copy_: 199 MB read and
            199 MB written) as the yardstick: the draw kernel reads no frame byte and writes only painted pixels, so the expectation to
            confirm or refute is draw < one copy of the frames.  The mean shader clock over the timed region is recorded beside it
-           (bench.py's Telemetry).
+           (bench.py's Telemetry).  Both loads also run with text labels (FrameOverlay(labels=True): class name, score and, on the
+           car box, the azimuth of yolo_pose_top1, in the default 6 x 11 font): yolo_overlay_labels and yolo_overlay_text take their
+           turns in the same alternation, so the expectation "at K = 2 the text kernel costs well below the draw kernel, because its
+           grid follows the label area" is read off one run.
   host     the route the overlay replaces, on the same box: a blocking D2H of the rows, intake.plate_matrix per frame, PIL
            ImageDraw.line for the box and the plate edges on the host's frames (cv2 is not installed here; PIL's line is the
            nearest thing), the H2D of the matrices; wall clock around device synchronises.  The comparison for "was it worth it", not
            the code under test.
   video    D53 at 416^2 bs 32 (--dtype, tune='auto') from resident 1080p uint8 frames: FrameIntake -> net -> predict_device ->
-           [FrameOverlay with the top-1 rows and resident plate rows] -> non-blocking D2H of the frames into pinned memory; wall
-           clock per step with and without the overlay, alternating blocks.  The plate rows are synthetic and resident (this net has
+           [pose_device ->] [FrameOverlay with the top-1 rows and resident plate rows] -> non-blocking D2H of the frames into pinned
+           memory; wall clock per step without the overlay, with it, and with it and its labels, alternating blocks.  The plate rows are synthetic and resident (this net has
            no plate branch); everything else is the product's path.
 
 The parent process never opens the GPU: every step runs as ONE fresh child process at a time under its own `timeout`, and the
@@ -31,7 +34,7 @@ sys.path.insert(0, ROOT)
 SRC_HW, BATCH, SIZE = (1080, 1920), 32, (416, 416)
 CAMERA = {'image_width': 1920, 'image_height': 1080,
           'projection_matrix': {'data': [1230.0, 0.0, 967.5, 0.0, 0.0, 1246.5, 536.0, 0.0, 0.0, 0.0, 1.0, 0.0]}}
-STEPS = (('kernels', 300), ('host', 300), ('video', 420))            # (step, seconds allowed)
+STEPS = (('kernels', 300), ('host', 300), ('video', 600))            # (step, seconds allowed)
 
 
 def _stat(v):
@@ -98,6 +101,7 @@ def _events_alternating(fns, warmup, iters):
 
 
 def step_kernels(args, dev):
+    import numpy as np
     import torch
     from bench import Telemetry
     from yolo_amd import lib as L
@@ -107,6 +111,11 @@ def step_kernels(args, dev):
     spare = torch.empty_like(frames)
     pred, lp, rows, kept, count = [torch.from_numpy(a).to(dev) for a in _rows(1)]
     ov = FrameOverlay(camera=CAMERA, device=dev)
+    ovl = FrameOverlay(camera=CAMERA, device=dev, labels=True, names=['car', 'truck'])
+    font = ovl.font
+    dirs = torch.tensor([[1.0, 0.0], [-1.0, 0.0]], dtype=torch.float32, device=dev)      # two classes: 0 and 180 degrees
+    pose = torch.empty((BATCH, 4), dtype=torch.float32, device=dev)
+    L.check(lib.yolo_pose_top1(L.ptr(pred), BATCH, 8, L.ptr(dirs), None, 0, 0, 0, None, L.ptr(pose), L.stream_ptr()), 'pose_top1')
     H, W = SRC_HW
     out = {'src': list(SRC_HW), 'batch': BATCH, 'warmup': args.warmup, 'iters': args.iters, 'clock': 'HIP events',
            'frame_batch_bytes': int(frames.numel())}
@@ -129,9 +138,41 @@ def step_kernels(args, dev):
         def whole():
             ov(work, **kw)
 
-        r = {'K': K, 'enabled_slots': int((tab[:, :, 10] != 0).sum())}
-        alt = _events_alternating({'draw': draw, 'd2d_copy': copy}, args.warmup, args.iters)
+        # the same load with labels: the label table FrameOverlay(labels=True) makes, then its two kernels through the ABI
+        kwl = dict(kw, pose=pose) if name == 'top1_plate' else kw
+        ovl(work, **kwl)
+        labels = ovl.labels
+        torch.cuda.synchronize()
+        assert torch.equal(ovl.table, table)
+        lab = labels.cpu().numpy()
+        fnt = ovl._font
+
+        def text():
+            L.check(lib.yolo_overlay_text(L.ptr(work), L.ptr(labels), L.ptr(fnt), font.nglyph, font.first_code, font.cell_w, font.cell_h,
+                                          font.advance, 1, 1, BATCH, H, W, 3, K, s), 'overlay_text')
+
+        if name == 'top1_plate':
+            def make_labels():
+                L.check(lib.yolo_overlay_labels(L.ptr(table), None, None, None, None, 0, 0, 0, 1, L.ptr(pred), 8, L.ptr(pose), 1, L.ptr(lp),
+                                                L.ptr(ovl._names), 2, font.cell_w, font.cell_h, font.advance, 1, 4, 1, 1, 0xff000000,
+                                                BATCH, H, W, K, L.ptr(labels), s), 'overlay_labels')
+        else:
+            def make_labels():
+                L.check(lib.yolo_overlay_labels(L.ptr(table), L.ptr(rows), L.ptr(kept), L.ptr(count), None, 400, 8, 100, 2, None, 0, None,
+                                                1, None, L.ptr(ovl._names), 2, font.cell_w, font.cell_h, font.advance, 1, 4, 1, 1,
+                                                0xff000000, BATCH, H, W, K, L.ptr(labels), s), 'overlay_labels')
+
+        def whole_labels():
+            ovl(work, **kwl)
+
+        r = {'K': K, 'enabled_slots': int((tab[:, :, 10] != 0).sum()), 'enabled_labels': int((lab[:, :, 4] & 1).sum()),
+             'label_chars': int(lab[:, :, 5].sum())}
+        alt = _events_alternating({'draw': draw, 'd2d_copy': copy, 'labels': make_labels, 'text': text}, args.warmup, args.iters)
+        assert np.array_equal(labels.cpu().numpy(), lab)                # the ABI call made the table FrameOverlay made
         r['overlay_draw'], r['d2d_copy_of_the_frames'] = _stat(alt['draw']), _stat(alt['d2d_copy'])
+        r['overlay_labels'], r['overlay_text'] = _stat(alt['labels']), _stat(alt['text'])
+        r['text_over_draw'] = r['overlay_text']['median_ms'] / r['overlay_draw']['median_ms']
+        r['whole_call_with_labels'] = _stat(_events(whole_labels, args.warmup, args.iters))     # + yolo_overlay_labels + yolo_overlay_text
         r['draw_over_copy'] = r['overlay_draw']['median_ms'] / r['d2d_copy_of_the_frames']['median_ms']
         r['d2d_copy_gb_per_s'] = 2 * frames.numel() / (r['d2d_copy_of_the_frames']['median_ms'] * 1e-3) / 1e9
         r['whole_call'] = _stat(_events(whole, args.warmup, args.iters))           # shapes (+ warp) + draw as FrameOverlay launches them
@@ -224,6 +265,7 @@ def step_video(args, dev):
     det = Detector(spec, SIZE, steps, device=dev)
     intake = FrameIntake(SIZE, device=dev)
     ov = FrameOverlay(camera=CAMERA, car_threshold=0.0, device=dev)     # (an untrained net: draw whatever it predicts)
+    ovl = FrameOverlay(camera=CAMERA, car_threshold=0.0, device=dev, labels=True, names=['az%03d' % (15 * k) for k in range(det.C - 6)])
     resident = _frames(0).to(dev)
     lp = torch.from_numpy(_rows(1)[1]).to(dev)
     pinned = torch.empty(resident.shape, dtype=torch.uint8, pin_memory=True)
@@ -238,7 +280,13 @@ def step_video(args, dev):
         out, _, _ = ov(intake.frames, pred=pred, lp=lp, out=annotated)
         pinned.copy_(out, non_blocking=True)
 
-    routes = {'without_overlay': plain, 'with_overlay': with_overlay}
+    def with_labels():
+        pred, _ = det.predict_device(net(intake(resident)))
+        pose, _ = det.pose_device(pred)
+        out, _, _ = ovl(intake.frames, pred=pred, lp=lp, pose=pose, out=annotated)
+        pinned.copy_(out, non_blocking=True)
+
+    routes = {'without_overlay': plain, 'with_overlay': with_overlay, 'with_overlay_and_labels': with_labels}
     for fn in routes.values():
         for _ in range(args.warmup):
             fn()
@@ -259,6 +307,7 @@ def step_video(args, dev):
     for k, v in wall.items():
         out[k] = dict(_stat(v), frames_per_s=BATCH / (float(sorted(v)[len(v) // 2]) * 1e-3))
     out['overlay_cost_ms_per_step'] = out['with_overlay']['median_ms'] - out['without_overlay']['median_ms']
+    out['labels_cost_ms_per_step'] = out['with_overlay_and_labels']['median_ms'] - out['with_overlay']['median_ms']
     print(json.dumps(out), flush=True)
     return out
 

@@ -23,9 +23,9 @@ def __getattr__(name):
     if name == 'BackgroundBank':
         from . import background
         return background.BackgroundBank
-    if name == 'FrameOverlay':
+    if name in ('FrameOverlay', 'BitmapFont', 'default_font'):
         from . import overlay
-        return overlay.FrameOverlay
+        return getattr(overlay, name)
     if name in ('fit_anchors', 'sample_sizes', 'anchor_quality', 'AnchorFit'):
         from . import anchors
         return getattr(anchors, name)

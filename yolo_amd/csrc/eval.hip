@@ -105,6 +105,22 @@ extern "C" int yolo_eval_match(const float* rows, const int* kept, const int* ke
 }
 
 // ---- yolo_eval_top1 ----------------------------------------------------------------------------
+// RadarProb.cls2ang's sums (yolo_cv.py:85-94): p = softmax(cls logits), (cs, sn) = (sum cos_c p_c, sum sin_c p_c).  The one place
+// this arithmetic lives: eval_top1_kernel and pose_top1_kernel return the same bits for the same row.
+__device__ __forceinline__ void top1_direction(const float* cl, int ncls, const float* __restrict__ class_dirs, float& cs, float& sn) {
+    float m = -FLT_MAX;
+    for (int c = 0; c < ncls; ++c) m = fmaxf(m, cl[c]);
+    float sum = 0.f;
+    for (int c = 0; c < ncls; ++c) sum += expf(cl[c] - m);
+    cs = 0.f;
+    sn = 0.f;
+    for (int c = 0; c < ncls; ++c) {
+        const float pc = expf(cl[c] - m) / sum;
+        cs += class_dirs[2 * c] * pc;
+        sn += class_dirs[2 * c + 1] * pc;
+    }
+}
+
 // One thread per image: pred row [score, y, x, h, w, rot, cls...] against object 0 of the image's labels.
 //   iou      get_iou(mode 2) of the box rebuilt as car/YOLO.py:518-521 rebuilds it (l = x - w/2, t = y - h/2, r = x + w/2, b = y + h/2)
 //   azimuth  atan2(sum sin_c p_c, sum cos_c p_c), p = softmax(cls logits): RadarProb.cls2ang, yolo_cv.py:85-95
@@ -120,18 +136,8 @@ __global__ __launch_bounds__(64) void eval_top1_kernel(const float* __restrict__
     const float y = p[1], x = p[2], h = p[3], w = p[4];
     const float4 box = make_float4(x - w / 2.f, y - h / 2.f, x + w / 2.f, y + h / 2.f);
     const float iou = get_iou_ref<2>(box, t[1], t[2], t[3], t[4]);
-    const int ncls = C - 6;
-    const float* cl = p + 6;
-    float m = -FLT_MAX;
-    for (int c = 0; c < ncls; ++c) m = fmaxf(m, cl[c]);
-    float sum = 0.f;
-    for (int c = 0; c < ncls; ++c) sum += expf(cl[c] - m);
-    float cs = 0.f, sn = 0.f;
-    for (int c = 0; c < ncls; ++c) {
-        const float pc = expf(cl[c] - m) / sum;
-        cs += class_dirs[2 * c] * pc;
-        sn += class_dirs[2 * c + 1] * pc;
-    }
+    float cs, sn;
+    top1_direction(p + 6, C - 6, class_dirs, cs, sn);
     float4 o;
     o.x = iou;
     o.y = atan2f(sn, cs);
@@ -147,6 +153,64 @@ extern "C" int yolo_eval_top1(const float* pred, const float* labels, const floa
     if ((reinterpret_cast<unsigned long long>(out) & 15ull) != 0) return YOLO_EINVAL;      // 16-byte rows
     YOLO_LAUNCH(eval_top1_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, pred, labels, class_dirs, out, B, C,
                 (long long)nobj * label_cols);
+    YOLO_LAUNCH_CHECK();
+    return YOLO_OK;
+}
+
+// ---- yolo_pose_top1 ----------------------------------------------------------------------------
+// The row Video.process publishes (car/video_node.py:235-255, car_and_LP/carLP_video_node.py:48-72), one thread per image:
+//   azimuth, radius   eval_top1_kernel's, through top1_direction
+//   class             the index of the largest class logit (strictly larger wins: the lowest index among equals, never a NaN)
+//   depth             depth[b][(int)(Hd y)][(int)(Wd x)] (:239-241), -1 without a depth image (:243) or where the index leaves it
+// rows_out may be pred itself: a thread has read its whole row (the logits above, column j just before it is stored) when it writes.
+__global__ __launch_bounds__(64) void pose_top1_kernel(const float* pred, const float* __restrict__ class_dirs,
+                                                       const float* __restrict__ depth, float* rows_out, float* __restrict__ pose,
+                                                       int B, int C, int Hd, int Wd, int row5) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const float* p = pred + (long long)b * C;
+    const int ncls = C - 6;
+    float cs, sn;
+    top1_direction(p + 6, ncls, class_dirs, cs, sn);
+    const float azimuth = atan2f(sn, cs);
+    const float radius = p[0] * sqrtf(sn * sn + cs * cs);
+    int cls = 0;
+    float top = -INFINITY;
+    for (int c = 0; c < ncls; ++c) {
+        const float v = p[6 + c];
+        if (v > top) { top = v; cls = c; }
+    }
+    float dep = -1.f;
+    if (depth) {
+        const double dx = (double)Wd * (double)p[2], dy = (double)Hd * (double)p[1];
+        // (false for a NaN or an infinity; the truncation toward zero makes (-1, 0) index 0)
+        if (dx > -1.0 && dx < (double)Wd && dy > -1.0 && dy < (double)Hd)
+            dep = depth[((long long)b * Hd + (int)dy) * Wd + (int)dx];
+    }
+    float4 o;
+    o.x = azimuth;
+    o.y = radius;
+    o.z = dep;
+    o.w = (float)cls;
+    if (rows_out) {
+        float* q = rows_out + (long long)b * C;
+        const float five = row5 == 1 ? azimuth : dep;
+        for (int j = 0; j < C; ++j) {
+            const float v = p[j];
+            q[j] = (j == 5 && row5 != 0) ? five : v;
+        }
+    }
+    reinterpret_cast<float4*>(pose)[b] = o;
+}
+
+extern "C" int yolo_pose_top1(const float* pred, int B, int C, const float* class_dirs, const float* depth, int Hd, int Wd, int row5,
+                              float* rows_out, float* pose, void* stream) {
+    if (!pred || !class_dirs || !pose) return YOLO_EINVAL;
+    if (B <= 0 || C <= 6 || row5 < 0 || row5 > 2) return YOLO_EINVAL;
+    if (depth && (Hd < 1 || Wd < 1)) return YOLO_EINVAL;
+    if ((reinterpret_cast<unsigned long long>(pose) & 15ull) != 0) return YOLO_EINVAL;     // 16-byte rows
+    YOLO_LAUNCH(pose_top1_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, pred, class_dirs, depth, rows_out, pose, B, C,
+                Hd, Wd, row5);
     YOLO_LAUNCH_CHECK();
     return YOLO_OK;
 }

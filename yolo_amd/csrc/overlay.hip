@@ -4,6 +4,9 @@
 //   overlay_shapes_kernel   one thread per (image, slot): the slot's four integer vertices, colour, thickness and enabled flag; the
 //                           plate's thread also solves the 8 x 8 system of the plate-image -> frame homography (fp64 Gaussian
 //                           elimination with partial pivoting) and writes the (9) fp32 matrix yolo_warp_u8_to_nchw reads, and lp_valid
+//   overlay_labels_kernel   one thread per (image, slot): the slot's label -- [name ' '] score [' ' degrees] as text bytes, placed over
+//                           the box's top-left corner and moved inside the frame (integers only)
+//   overlay_text_kernel     one block per tile of one LABEL's rectangle (not of the frame): bitmap-font text and its ground box
 //   overlay_draw_kernel     one block per 256 x 32 pixel tile of one image: the image's 4 K segments go to LDS with their
 //                           t/2-expanded bounding boxes, wave 0 compacts those that meet the tile (ballot + popcount: ordered, no
 //                           atomics), and each thread tests its pixels against the list from the highest slot down -- the first hit is
@@ -12,6 +15,7 @@
 // The draw kernel reads no frame byte and stores only painted pixels (byte stores: the frame may start at any address); a tile no
 // segment meets leaves after the compaction, so an image without an enabled shape is never addressed.
 #include "common.h"
+#include <float.h>
 
 constexpr int OV_SLOT_WORDS = YOLO_OVERLAY_SLOT_WORDS;  // x0 y0 x1 y1 x2 y2 x3 y3 colour thickness enabled pad
 constexpr int OV_MAX_K = YOLO_OVERLAY_MAX_SLOTS;
@@ -373,5 +377,335 @@ extern "C" int yolo_overlay_draw(unsigned char* frames, const int* table, int N,
         case 2: return overlay_draw_launch<2>(frames, table, N, H, W, K, s);
         case 3: return overlay_draw_launch<3>(frames, table, N, H, W, K, s);
         default: return overlay_draw_launch<4>(frames, table, N, H, W, K, s);
+    }
+}
+
+// ---- labels ---------------------------------------------------------------------------------------------------------------------
+
+constexpr int OV_LABEL_WORDS = YOLO_OVERLAY_LABEL_WORDS;  // x y text-colour ground-colour flags nchar text[10]
+constexpr int OV_LABEL_CHARS = YOLO_OVERLAY_LABEL_CHARS;
+constexpr int OV_NAME_BYTES = YOLO_OVERLAY_NAME_BYTES;
+constexpr int OV_MAX_CELL = 32;
+constexpr int OV_MAX_SCALE = 16;
+constexpr long long OV_LABEL_SAT = 1LL << 30;             // x and y are made in 64 bits and saturated to +-2^30 (the raster refuses beyond 2^20)
+
+struct OverlayLabelsArgs {
+    const int* table;
+    const float* rows; const int* kept; const int* kept_count; const float* kept_scores; int nbox, rows_C, post_nms, cand_per_box;
+    const float* pred; int pred_C; const float* pose; int show_deg;
+    const float* lp;
+    const unsigned char* names; int nname;
+    int cell_w, cell_h, advance, scale, gap, pad, ground; unsigned ground_colour;
+    int B, H, W, K;
+    int* labels;
+};
+
+__device__ __forceinline__ int overlay_put(unsigned* text, int n, unsigned ch) {
+    text[n >> 2] |= (ch & 255u) << (8 * (n & 3));
+    return n + 1;
+}
+
+// [name ' '] score [' ' deg] -> text bytes, returns nchar (at most 16 + 1 + 5 + 1 + 4 = 27)
+__device__ int overlay_compose(unsigned* text, const unsigned char* name, float score, bool have_deg, float azimuth) {
+    int n = 0;
+    if (name && name[0] != 0) {
+        for (int i = 0; i < OV_NAME_BYTES && name[i] != 0; ++i) n = overlay_put(text, n, name[i]);
+        n = overlay_put(text, n, ' ');
+    }
+    if (score >= 0.f && score <= FLT_MAX) {
+        // (double)score * 1000.0 is exact (24 x 10 significant bits): the nearest integer, ties to even, is '%.3f' digit for digit
+        const double d = (double)score * 1000.0;
+        const int v = d >= 9999.0 ? 9999 : (int)llrint(d);
+        n = overlay_put(text, n, '0' + v / 1000);
+        n = overlay_put(text, n, '.');
+        n = overlay_put(text, n, '0' + (v / 100) % 10);
+        n = overlay_put(text, n, '0' + (v / 10) % 10);
+        n = overlay_put(text, n, '0' + v % 10);
+    } else {
+        n = overlay_put(text, n, '-');
+        n = overlay_put(text, n, '.');
+        for (int i = 0; i < 3; ++i) n = overlay_put(text, n, '-');
+    }
+    if (have_deg && fabsf(azimuth) <= FLT_MAX) {
+        const double d = rint((double)azimuth * 57.29577951308232);
+        if (fabs(d) <= 999.0) {
+            int v = (int)d;
+            n = overlay_put(text, n, ' ');
+            if (v < 0) { n = overlay_put(text, n, '-'); v = -v; }
+            if (v >= 100) n = overlay_put(text, n, '0' + v / 100);
+            if (v >= 10) n = overlay_put(text, n, '0' + (v / 10) % 10);
+            n = overlay_put(text, n, '0' + v % 10);
+        }
+    }
+    return n;
+}
+
+__device__ __forceinline__ int overlay_sat(long long v) {
+    return (int)(v < -OV_LABEL_SAT ? -OV_LABEL_SAT : v > OV_LABEL_SAT ? OV_LABEL_SAT : v);
+}
+
+__global__ __launch_bounds__(OV_SHAPE_THREADS) void overlay_labels_kernel(OverlayLabelsArgs a) {
+    const int q = blockIdx.x * OV_SHAPE_THREADS + threadIdx.x;
+    if (q >= a.B * a.K) return;
+    const int b = q / a.K, s = q - b * a.K;
+    const int4* slot4 = reinterpret_cast<const int4*>(a.table + (long long)q * OV_SLOT_WORDS);
+    const int4 q0 = slot4[0], q1 = slot4[1], q2 = slot4[2];
+    const int n_nms = a.rows ? a.post_nms : 0;
+    const int s_pred = a.pred ? n_nms : -1;
+    bool on = q2.z != 0;
+    float score = 0.f, azimuth = 0.f;
+    int cls = -1;
+    bool have_deg = false;
+    if (s < n_nms) {
+        // the id test of overlay_shapes_kernel again: no row is read through an id it refused
+        int cnt = a.kept_count[b];
+        cnt = cnt < a.post_nms ? cnt : a.post_nms;
+        const int id = s < cnt ? a.kept[(long long)b * a.post_nms + s] : -1;
+        const int box = id >= 0 ? id / a.cand_per_box : -1;
+        on = on && box >= 0 && box < a.nbox;
+        if (on) {
+            cls = a.cand_per_box > 1 ? id % a.cand_per_box : -1;
+            score = a.kept_scores ? a.kept_scores[(long long)b * a.post_nms + s] : a.rows[((long long)b * a.nbox + box) * a.rows_C];
+        }
+    } else if (s == s_pred) {
+        score = a.pred[(long long)b * a.pred_C];
+        if (a.pose) {
+            const float4 po = reinterpret_cast<const float4*>(a.pose)[b];
+            if (po.w > -1.f && po.w < (float)a.nname) cls = (int)po.w;      // (false for a NaN)
+            have_deg = a.show_deg != 0;
+            azimuth = po.x;
+        }
+    } else {
+        score = a.lp[(long long)b * 7];
+    }
+    unsigned text[OV_LABEL_CHARS / 4];
+#pragma unroll
+    for (int i = 0; i < OV_LABEL_CHARS / 4; ++i) text[i] = 0u;
+    int nchar = 0, x = 0, y = 0;
+    if (on) {
+        const unsigned char* name = (cls >= 0 && cls < a.nname) ? a.names + (long long)cls * OV_NAME_BYTES : nullptr;
+        nchar = overlay_compose(text, name, score, have_deg, azimuth);
+        const long long bx0 = min(min(q0.x, q0.z), min(q1.x, q1.z)), by0 = min(min(q0.y, q0.w), min(q1.y, q1.w));
+        const long long Th = (long long)a.cell_h * a.scale, Tw = ((long long)(nchar - 1) * a.advance + a.cell_w) * a.scale;
+        long long ly = by0 - a.gap - Th;
+        if (ly - a.pad < 0) ly = by0 + a.gap;                            // no room above: under the box's top edge
+        long long lx = bx0;
+        if (lx + Tw + a.pad > a.W) lx = (long long)a.W - Tw - a.pad;
+        if (lx - a.pad < 0) lx = a.pad;
+        x = overlay_sat(lx);
+        y = overlay_sat(ly);
+    }
+    int4* out = reinterpret_cast<int4*>(a.labels + (long long)q * OV_LABEL_WORDS);
+    out[0] = make_int4(x, y, on ? q2.x : 0, on ? (int)a.ground_colour : 0);
+    out[1] = make_int4(on ? (1 | (a.ground ? 2 : 0)) : 0, nchar, (int)text[0], (int)text[1]);
+    out[2] = make_int4((int)text[2], (int)text[3], (int)text[4], (int)text[5]);
+    out[3] = make_int4((int)text[6], (int)text[7], (int)text[8], (int)text[9]);
+}
+
+extern "C" int yolo_overlay_labels(const int* table, const float* rows, const int* kept, const int* kept_count, const float* kept_scores,
+                                   int nbox, int rows_C, int post_nms, int cand_per_box, const float* pred, int pred_C,
+                                   const float* pose, int show_deg, const float* lp, const unsigned char* names, int nname, int cell_w,
+                                   int cell_h, int advance, int scale, int gap, int pad, int ground, unsigned ground_colour, int B,
+                                   int H, int W, int K, int* labels, void* stream) {
+    if (!table || !labels || B <= 0 || H <= 0 || W <= 0 || K <= 0) return YOLO_EINVAL;
+    if (!rows && !pred && !lp) return YOLO_EINVAL;
+    if (rows && (!kept || !kept_count || nbox <= 0 || rows_C < 5 || post_nms <= 0 || cand_per_box <= 0)) return YOLO_EINVAL;
+    if (pred && pred_C < 6) return YOLO_EINVAL;
+    if (K != (rows ? post_nms : 0) + (pred ? 1 : 0) + (lp ? 1 : 0)) return YOLO_EINVAL;
+    if (nname < 0 || (nname > 0 && !names)) return YOLO_EINVAL;
+    if (cell_w < 1 || cell_h < 1 || scale < 1 || advance < cell_w || gap < 0 || pad < 0) return YOLO_EINVAL;
+    if (ground != 0 && ground != 1) return YOLO_EINVAL;
+    if ((reinterpret_cast<unsigned long long>(table) & 15ull) || (reinterpret_cast<unsigned long long>(labels) & 15ull) ||
+        (reinterpret_cast<unsigned long long>(pose) & 15ull))
+        return YOLO_EINVAL;
+    if (K > OV_MAX_K || cell_w > OV_MAX_CELL || cell_h > OV_MAX_CELL || scale > OV_MAX_SCALE || H > OV_MAX_SIDE || W > OV_MAX_SIDE)
+        return YOLO_EUNSUPPORTED;
+    if ((long long)B * K > 0x7fffff00LL) return YOLO_EUNSUPPORTED;
+    OverlayLabelsArgs a;
+    a.table = table;
+    a.rows = rows; a.kept = kept; a.kept_count = kept_count; a.kept_scores = kept_scores; a.nbox = nbox; a.rows_C = rows_C;
+    a.post_nms = post_nms; a.cand_per_box = cand_per_box;
+    a.pred = pred; a.pred_C = pred_C; a.pose = pose; a.show_deg = show_deg; a.lp = lp; a.names = names; a.nname = nname;
+    a.cell_w = cell_w; a.cell_h = cell_h; a.advance = advance; a.scale = scale; a.gap = gap; a.pad = pad; a.ground = ground;
+    a.ground_colour = ground_colour;
+    a.B = B; a.H = H; a.W = W; a.K = K; a.labels = labels;
+    const unsigned grid = (unsigned)(((long long)B * K + OV_SHAPE_THREADS - 1) / OV_SHAPE_THREADS);
+    YOLO_LAUNCH(overlay_labels_kernel, dim3(grid), dim3(OV_SHAPE_THREADS), 0, (hipStream_t)stream, a);
+    YOLO_LAUNCH_CHECK();
+    return YOLO_OK;
+}
+
+// ---- text -----------------------------------------------------------------------------------------------------------------------
+// The grid follows the labels, not the frame: block (tile, k, image) owns one OV_TEXT_TILE_W x OV_TEXT_TILE_H tile of label k's
+// paint rectangle (its ground box, or its text box without a ground) clipped to the frame; the grid holds as many tiles as the
+// largest label these metrics allow, and a block whose tile lies beyond its label's rectangle, or whose label is disabled or empty,
+// leaves at once.  The block keeps the font rows of the label's characters in LDS (row r of character i at [i cell_h + r]; a byte
+// outside the font: zeros), and the paint rectangles of the enabled labels ABOVE k that meet the tile (wave 0 compacts them: ballot
+// + popcount, no atomics).  A thread owns one column of the tile -- its character, glyph column and ground membership are fixed --
+// and walks the rows; a pixel is stored iff label k paints it and no label above does, so every pixel has one writer whatever the
+// block order.  Byte stores, no frame byte read.
+
+constexpr int OV_TEXT_THREADS = 256;
+constexpr int OV_TEXT_TILE_W = OV_TEXT_THREADS;         // one column per thread
+constexpr int OV_TEXT_TILE_H = 16;
+constexpr int OV_TEXT_CLAMP = 1 << 22;                  // an advance x scale or a pad beyond this acts like this inside any frame
+
+struct OverlayTextArgs {
+    int nglyph, first_code, cell_h, scale, step, pad, cw_px, th;      // step = advance x scale, cw_px = cell_w x scale, th = cell_h x scale
+    int H, W, K, tiles_x;
+};
+
+struct OverlayTextRect {
+    int x0, y0, x1, y1;                                  // the pixels a label may paint, [x0, x1) x [y0, y1), not clipped
+    int x, y, nchar, ground;
+};
+
+// words 0..7 of a label -> its paint rectangle; false: not enabled, or no character (such a label paints nothing)
+__device__ __forceinline__ bool overlay_text_rect(const int4 q0, const int4 q1, const OverlayTextArgs& a, OverlayTextRect& r) {
+    const int x = q0.x, y = q0.y, flags = q1.x, nchar = q1.y;
+    if (!(flags & 1) || nchar < 1 || nchar > OV_LABEL_CHARS) return false;
+    if (x < -OV_MAX_COORD || x > OV_MAX_COORD || y < -OV_MAX_COORD || y > OV_MAX_COORD) return false;
+    const int tw = (nchar - 1) * a.step + a.cw_px;       // < 39 x 2^22 + 2^9
+    const int grow = (flags & 2) ? a.pad : 0;
+    r.x0 = x - grow; r.x1 = x + tw + grow; r.y0 = y - grow; r.y1 = y + a.th + grow;
+    r.x = x; r.y = y; r.nchar = nchar; r.ground = (flags & 2) ? 1 : 0;
+    return true;
+}
+
+// is (px, py), a pixel inside the label's text box, ink?  The label's text and the font come from global memory: this is the path of
+// a label ABOVE the block's own that has no ground box.
+__device__ bool overlay_text_ink(const int* __restrict__ lab, const unsigned* __restrict__ font, const OverlayTextArgs& a, int px, int py) {
+    const int rx = px - lab[0], ty = py - lab[1];
+    const int i = rx / a.step, cx = rx - i * a.step;
+    if (cx >= a.cw_px) return false;
+    const long long g = (long long)(((unsigned)lab[6 + (i >> 2)] >> (8 * (i & 3))) & 255u) - a.first_code;
+    if (g < 0 || g >= a.nglyph) return false;
+    return (font[g * a.cell_h + ty / a.scale] >> (cx / a.scale)) & 1u;
+}
+
+template <int C>
+__global__ __launch_bounds__(OV_TEXT_THREADS) void overlay_text_kernel(unsigned char* __restrict__ frames, const int* __restrict__ labels,
+                                                                       const unsigned* __restrict__ font, OverlayTextArgs a) {
+    __shared__ unsigned glyph[OV_LABEL_CHARS * OV_MAX_CELL];
+    __shared__ OverlayTextRect cand[OV_MAX_K];
+    __shared__ unsigned char meets[OV_MAX_K];
+    __shared__ unsigned char list[OV_MAX_K];             // positions in cand[] of the labels above that meet the tile
+    __shared__ int n_list;
+    const int tid = threadIdx.x;
+    const int k = blockIdx.y;
+    const long long n = blockIdx.z;
+    const int* img_labels = labels + n * a.K * OV_LABEL_WORDS;
+    const int* lab = img_labels + k * OV_LABEL_WORDS;
+    const int4* lab4 = reinterpret_cast<const int4*>(lab);
+    const int4 q0 = lab4[0], q1 = lab4[1];
+    OverlayTextRect own;
+    if (!overlay_text_rect(q0, q1, a, own)) return;      // (the same for every thread of the block, as every return before the barriers)
+    const int cx0 = max(own.x0, 0), cy0 = max(own.y0, 0), cx1 = min(own.x1, a.W), cy1 = min(own.y1, a.H);
+    const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
+    // (cx0 <= 2^20 + 2^22 and tx < 64: no overflow)
+    const int x_lo = cx0 + tx * OV_TEXT_TILE_W, y_lo = cy0 + ty * OV_TEXT_TILE_H;
+    if (x_lo >= cx1 || y_lo >= cy1) return;
+    const int x_hi = min(x_lo + OV_TEXT_TILE_W, cx1), y_hi = min(y_lo + OV_TEXT_TILE_H, cy1);      // exclusive
+    for (int e = tid; e < own.nchar * a.cell_h; e += OV_TEXT_THREADS) {
+        const int i = e / a.cell_h, r = e - i * a.cell_h;
+        const long long g = (long long)(((unsigned)lab[6 + (i >> 2)] >> (8 * (i & 3))) & 255u) - a.first_code;
+        glyph[e] = (g >= 0 && g < a.nglyph) ? font[g * a.cell_h + r] : 0u;
+    }
+    const int n_above = a.K - 1 - k;                     // <= 127: one pass
+    if (tid < n_above) {
+        const int4* h4 = reinterpret_cast<const int4*>(img_labels + (k + 1 + tid) * OV_LABEL_WORDS);
+        OverlayTextRect r;
+        bool on = overlay_text_rect(h4[0], h4[1], a, r);
+        on = on && r.x0 < x_hi && r.x1 > x_lo && r.y0 < y_hi && r.y1 > y_lo;
+        if (on) cand[tid] = r;
+        meets[tid] = on ? 1 : 0;
+    }
+    __syncthreads();
+    if (tid < 64) {
+        int base = 0;
+        for (int g0 = 0; g0 < n_above; g0 += 64) {
+            const int g = g0 + tid;
+            const bool on = g < n_above && meets[g] != 0;
+            const unsigned long long mask = __ballot(on);
+            if (on) list[base + __popcll(mask & ((1ull << tid) - 1ull))] = (unsigned char)g;
+            base += __popcll(mask);
+        }
+        if (tid == 0) n_list = base;
+    }
+    __syncthreads();
+    const int px = x_lo + tid;
+    if (px >= x_hi) return;
+    const int count = n_list;
+    // the column's character and glyph column in the own label (ichar < 0: between two cells, or beside the text in the ground box)
+    const int rx = px - own.x;
+    int ichar = -1, col = 0;
+    if (rx >= 0) {
+        const int i = rx / a.step, cx = rx - i * a.step;
+        if (i < own.nchar && cx < a.cw_px) { ichar = i; col = cx / a.scale; }
+    }
+    if (ichar < 0 && !own.ground) return;
+    const unsigned ink_colour = (unsigned)q0.z, ground_colour = (unsigned)q0.w;
+    unsigned char* img = frames + n * a.H * a.W * C;
+    for (int py = y_lo; py < y_hi; ++py) {
+        const int ry = py - own.y;
+        bool ink = false;
+        if (ichar >= 0 && ry >= 0 && ry < a.th) ink = (glyph[ichar * a.cell_h + ry / a.scale] >> col) & 1u;
+        if (!ink && !own.ground) continue;
+        bool covered = false;
+        for (int e = 0; e < count && !covered; ++e) {
+            const int h = list[e];
+            const OverlayTextRect& r = cand[h];
+            if (px < r.x0 || px >= r.x1 || py < r.y0 || py >= r.y1) continue;
+            covered = r.ground ? true : overlay_text_ink(img_labels + (k + 1 + h) * OV_LABEL_WORDS, font, a, px, py);
+        }
+        if (covered) continue;
+        const unsigned colour = ink ? ink_colour : ground_colour;
+        unsigned char* p = img + ((long long)py * a.W + px) * C;
+#pragma unroll
+        for (int c = 0; c < C; ++c) p[c] = (unsigned char)(colour >> (8 * c));
+    }
+}
+
+template <int C>
+static int overlay_text_launch(unsigned char* frames, const int* labels, const unsigned* font, const OverlayTextArgs& a, int tiles,
+                               int N, hipStream_t stream) {
+    const long long img = (long long)a.H * a.W * C;
+    for (int n0 = 0; n0 < N; n0 += 65535) {              // (grid.z holds at most 65535 images)
+        const int nb = N - n0 < 65535 ? N - n0 : 65535;
+        YOLO_LAUNCH((overlay_text_kernel<C>), dim3(tiles, a.K, nb), dim3(OV_TEXT_THREADS), 0, stream, frames + n0 * img,
+                    labels + (long long)n0 * a.K * OV_LABEL_WORDS, font, a);
+        YOLO_LAUNCH_CHECK();
+    }
+    return YOLO_OK;
+}
+
+extern "C" int yolo_overlay_text(unsigned char* frames, const int* labels, const unsigned* font, int nglyph, int first_code, int cell_w,
+                                 int cell_h, int advance, int scale, int pad, int N, int H, int W, int C, int K, void* stream) {
+    if (!frames || !labels || !font) return YOLO_EINVAL;
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || nglyph <= 0 || cell_w <= 0 || cell_h <= 0 || scale <= 0) return YOLO_EINVAL;
+    if (advance < cell_w || pad < 0) return YOLO_EINVAL;
+    if ((reinterpret_cast<unsigned long long>(labels) & 15ull) || (reinterpret_cast<unsigned long long>(font) & 3ull)) return YOLO_EINVAL;
+    if (K > OV_MAX_K || C > OV_MAX_C || H > OV_MAX_SIDE || W > OV_MAX_SIDE || cell_w > OV_MAX_CELL || cell_h > OV_MAX_CELL ||
+        scale > OV_MAX_SCALE || nglyph > 256)
+        return YOLO_EUNSUPPORTED;
+    OverlayTextArgs a;
+    a.nglyph = nglyph; a.first_code = first_code; a.cell_h = cell_h; a.scale = scale;
+    // with |x| <= 2^20 and a frame of at most 2^14 pixels a side, a second cell 2^22 pixels on, or a ground box grown by 2^22, is where
+    // any larger value would put it for every pixel of the frame
+    const long long step = (long long)advance * scale;
+    a.step = step > OV_TEXT_CLAMP ? OV_TEXT_CLAMP : (int)step;
+    a.pad = pad > OV_TEXT_CLAMP ? OV_TEXT_CLAMP : pad;
+    a.cw_px = cell_w * scale; a.th = cell_h * scale;
+    a.H = H; a.W = W; a.K = K;
+    const long long max_w = (long long)(OV_LABEL_CHARS - 1) * a.step + a.cw_px + 2LL * a.pad, max_h = (long long)a.th + 2LL * a.pad;
+    const int span_w = (int)(max_w < W ? max_w : W), span_h = (int)(max_h < H ? max_h : H);
+    a.tiles_x = (span_w + OV_TEXT_TILE_W - 1) / OV_TEXT_TILE_W;
+    const int tiles = a.tiles_x * ((span_h + OV_TEXT_TILE_H - 1) / OV_TEXT_TILE_H);               // <= 64 x 1024
+    hipStream_t s = (hipStream_t)stream;
+    switch (C) {
+        case 1: return overlay_text_launch<1>(frames, labels, font, a, tiles, N, s);
+        case 2: return overlay_text_launch<2>(frames, labels, font, a, tiles, N, s);
+        case 3: return overlay_text_launch<3>(frames, labels, font, a, tiles, N, s);
+        default: return overlay_text_launch<4>(frames, labels, font, a, tiles, N, s);
     }
 }

@@ -47,6 +47,7 @@ class Detector(object):
         self._lib = L.load()
         self._nms_ws = {}
         self._host = {}
+        self._dirs = {}                   # class azimuths -> device (ncls, 2) [cos, sin]
 
     def _merged(self, outs):
         """Accepts the list of per-scale outputs (fine->coarse) or an already merged (B,N,A,C) tensor."""
@@ -112,6 +113,50 @@ class Detector(object):
         L.check(self._lib.yolo_predict_top1(L.ptr(m), L.ptr(pred), L.ptr(idx), B, self.C, C.byref(self.grid),
                                             L.stream_ptr()), 'predict_top1')
         return pred, idx
+
+    def pose_device(self, pred, depth=None, row5=None, out=None, class_azimuth_deg=None):
+        """What Video.process does with the top-1 row (car/video_node.py:235-255, car_and_LP/carLP_video_node.py:48-72), on the
+        device: pred (B,C) rows of predict_device -> (pose (B,4) float32 [azimuth (rad, RadarProb.cls2ang), radius, depth, class],
+        rows (B,C): the published rows, column 5 left alone (row5=None), set to the azimuth ('azimuth') or to the depth ('depth')).
+        depth: None (pose[:, 2] = -1) or a float32 (B,Hd,Wd) device tensor, one depth frame per image, read at the box centre; -1
+        where the centre lies outside the frame.  out: the tensor to take the rows (may be pred itself), else a new one.
+        class_azimuth_deg: the azimuth of every class, k * 360 / ncls by default (car/video_node.py:37-38), as Evaluator's.  Runs
+        on the current stream and does not synchronise."""
+        L.require_current_device(self.device, 'this Detector')
+        ncls = self.C - 6
+        if ncls < 1:
+            raise ValueError('the azimuth needs class logits (C > 6)')
+        if (not torch.is_tensor(pred) or pred.dtype != torch.float32 or pred.device != self.device or pred.dim() != 2
+                or pred.shape[1] != self.C or pred.shape[0] < 1 or not pred.is_contiguous()):
+            raise ValueError('pred should be a contiguous float32 tensor (B, %d) on %s' % (self.C, self.device))
+        B = int(pred.shape[0])
+        try:
+            mode = {None: 0, 'azimuth': 1, 'depth': 2}[row5]
+        except (KeyError, TypeError):
+            raise ValueError("row5 should be None, 'azimuth' or 'depth'")
+        Hd = Wd = 0
+        if depth is not None:
+            if (not torch.is_tensor(depth) or depth.dtype != torch.float32 or depth.device != self.device or depth.dim() != 3
+                    or depth.shape[0] != B or 0 in depth.shape or not depth.is_contiguous()):
+                raise ValueError('depth should be a contiguous float32 tensor (%d, Hd, Wd) on %s' % (B, self.device))
+            Hd, Wd = int(depth.shape[1]), int(depth.shape[2])
+        if out is None:
+            out = torch.empty_like(pred)
+        elif (not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != self.device
+              or tuple(out.shape) != tuple(pred.shape) or not out.is_contiguous()):
+            raise ValueError('out should be a contiguous float32 tensor of shape %r on %s' % (tuple(pred.shape), self.device))
+        key = None if class_azimuth_deg is None else tuple(float(v) for v in np.asarray(class_azimuth_deg, np.float64).reshape(-1))
+        dirs = self._dirs.get(key)
+        if dirs is None:
+            az = np.asarray([k * 360.0 / ncls for k in range(ncls)] if key is None else key, np.float64)
+            if az.shape[0] != ncls:
+                raise ValueError('class_azimuth_deg should have one entry per class')
+            d = np.stack([np.cos(np.radians(az)), np.sin(np.radians(az))], axis=1).astype(np.float32)
+            dirs = self._dirs[key] = torch.from_numpy(d).to(self.device)
+        pose = torch.empty((B, 4), dtype=torch.float32, device=self.device)
+        L.check(self._lib.yolo_pose_top1(L.ptr(pred), B, self.C, L.ptr(dirs), L.ptr(depth), Hd, Wd, mode, L.ptr(out), L.ptr(pose),
+                                         L.stream_ptr()), 'pose_top1')
+        return pose, out
 
     def predict(self, outs):
         """YOLO.predict: np.float32 (B, 6+ncls) rows [score, y, x, h, w, rot, cls...] (D2H here)."""

@@ -96,6 +96,9 @@ SIGNATURES = {
     'yolo_overlay_shapes': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _i, _u, _vp, _d, _d, _d, _d, _i, _i, _f, _u, _i, _i,
                                  _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     'yolo_overlay_draw': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'yolo_overlay_labels': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _u, _i, _i,
+                                 _i, _i, _vp, _vp]),
+    'yolo_overlay_text': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'yolo_upsample2x_concat': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'yolo_decode': (_i, [_vp, _vp, _i, _i, C.POINTER(GridDesc), _vp]),
     'yolo_decode_scores': (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(GridDesc), _i, _vp]),
@@ -113,6 +116,7 @@ SIGNATURES = {
     'yolo_eval_match_supported': (_i, [_i, _i]),
     'yolo_eval_match': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     'yolo_eval_top1': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'yolo_pose_top1': (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     'yolo_pack_conv_weights_dgrad': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'yolo_pack_conv_weights_dgrad_s2': (_i, [_vp, _vp, _i, _i, _i, _vp]),
     'yolo_conv_dgrad_s2': (_i, [C.POINTER(ConvDesc), _vp]),

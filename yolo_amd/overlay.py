@@ -5,16 +5,24 @@ never leave the device.
                                                            + CarLPVideo.visualize_carlp (car_and_LP/carLP_video_node.py:74-86):
                                                            ProjectRectangle6D.add_edges (licence_plate_render/__init__.py:379-402)
 
+  FrameOverlay(..., labels=True, names=)(..., pose=)    <- what cv2_add_bbox_text (yolo_cv.py:273-282) is for: class, score and azimuth
+                                                           on every box, in a bitmap font (BitmapFont / default_font)
+
 Three launches on the current stream, no synchronisation: yolo_overlay_shapes (the shape table, the plate's inverse map and lp_valid,
 include/yolo_amd.h), yolo_warp_u8_to_nchw (the clipped plate, read from the frames BEFORE they are drawn on, as add_edges clips before
-it draws), yolo_overlay_draw.  The pixels are this library's own rule (4 dist^2 <= t^2, exact), not cv2.polylines': cv2 is not
-installed here.  Text labels (cv2_add_bbox_text), the radar plot and the depth lookup are not offered."""
+it draws), yolo_overlay_draw.  With labels=True two more: yolo_overlay_labels after the shapes (the text and place of every slot's
+label), yolo_overlay_text after the draw (the text lies over every shape).  The pixels are this library's own rules (4 dist^2 <= t^2
+for lines, the font's bits for text, both exact), not cv2.polylines' or cv2.putText's: cv2 is not installed here.  The azimuth and
+the depth lookup of Video.process are Detector.pose_device (yolo_pose_top1).  The radar plot is not offered."""
 import numpy as np
 
 from . import lib as L
 
 SLOT_WORDS = 12
 MAX_SLOTS = 128
+LABEL_WORDS = 16
+LABEL_CHARS = 40
+NAME_BYTES = 16
 # yolo_cv._color (yolo_modules/yolo_cv.py:11-20); cv2_add_bbox is called with index 4 (car/video_node.py:317)
 PALETTE = ((255, 255, 0), (255, 0, 255), (0, 255, 255), (0, 0, 255), (0, 255, 0), (255, 0, 0), (255, 255, 255), (0, 0, 0))
 
@@ -29,6 +37,53 @@ def _colour4(c):
 def _pack(c):
     c = _colour4(c)
     return c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24)
+
+
+class BitmapFont(object):
+    """A fixed-cell bitmap font for yolo_overlay_text: masks (nglyph, cell_h) uint32, bit c of masks[g][r] (bit 0 = the leftmost
+    column) the ink of column c, row r of the glyph of byte first_code + g; cell_w <= 32 columns, cell_h <= 32 rows, at most 256
+    glyphs; advance (default cell_w) is the distance between two cell origins in font pixels."""
+
+    def __init__(self, masks, cell_w, advance=None, first_code=32):
+        masks = np.ascontiguousarray(masks)
+        if masks.ndim != 2 or masks.dtype.kind not in 'iu' or not 1 <= masks.shape[0] <= 256 or not 1 <= masks.shape[1] <= 32:
+            raise ValueError('masks should be an integer array (1..256 glyphs, 1..32 rows)')
+        self.cell_w, self.cell_h = int(cell_w), int(masks.shape[1])
+        if not 1 <= self.cell_w <= 32:
+            raise ValueError('cell_w should be in 1..32')
+        if masks.min() < 0 or int(masks.max()) >> self.cell_w:
+            raise ValueError('a mask has ink outside its %d columns' % self.cell_w)
+        self.masks = masks.astype(np.uint32)
+        self.advance = self.cell_w if advance is None else int(advance)
+        if self.advance < self.cell_w:
+            raise ValueError('advance should be at least cell_w')
+        self.first_code = int(first_code)
+        self.nglyph = int(masks.shape[0])
+
+
+def default_font():
+    """PIL's built-in bitmap font as a BitmapFont: the codes 32..126, each rendered once into a mode-'L' cell and thresholded.
+    Nothing of PIL's is stored in this package; where this PIL has no bitmap font, bring one: FrameOverlay(font=BitmapFont(...))."""
+    from PIL import Image, ImageDraw, ImageFont
+    if hasattr(ImageFont, 'load_default_imagefont'):
+        font = ImageFont.load_default_imagefont()
+    else:
+        font = ImageFont.load_default()
+        if not isinstance(font, ImageFont.ImageFont):
+            raise RuntimeError('this PIL has no built-in bitmap font (load_default() gave %s): pass font=BitmapFont(...) to '
+                               'FrameOverlay' % type(font).__name__)
+    codes = range(32, 127)
+    boxes = [font.getbbox(chr(c)) for c in codes]
+    cell_w, cell_h = max(b[2] for b in boxes), max(b[3] for b in boxes)
+    if not (1 <= cell_w <= 32 and 1 <= cell_h <= 32):
+        raise RuntimeError('PIL\'s built-in font has %d x %d cells, beyond 32 x 32: pass font=BitmapFont(...)' % (cell_w, cell_h))
+    masks = np.zeros((len(codes), cell_h), np.uint32)
+    weights = (1 << np.arange(cell_w)).astype(np.uint32)
+    for g, c in enumerate(codes):
+        cell = Image.new('L', (cell_w, cell_h), 0)
+        ImageDraw.Draw(cell).text((0, 0), chr(c), fill=255, font=font)
+        masks[g] = ((np.asarray(cell) >= 128) * weights).sum(axis=1)
+    return BitmapFont(masks, cell_w, first_code=32)
 
 
 class FrameOverlay(object):
@@ -46,10 +101,20 @@ class FrameOverlay(object):
     determine a map).  out=None draws in place; otherwise frames is copied into out (same shape) and out is drawn on and returned.
     Buffers are cached per batch size: after the first call with a size nothing is allocated, and `clipped`, `lp_valid` and the
     attributes table / vertices / matrices (the device-made shape table of the last call) are THE OBJECT'S buffers, overwritten by the
-    next call with that size.  Runs on the current stream and does not synchronise."""
+    next call with that size.  Runs on the current stream and does not synchronise.
+
+    labels=True writes a text label on every enabled shape, [name ' '] score [' ' degrees], over the box's top-left corner (moved
+    inside the frame where it would leave it), in `font` (a BitmapFont; None: default_font()) enlarged font_scale times, label_gap
+    pixels from the box, on a ground box of colour label_ground grown by label_pad pixels (None: no ground box), in the shape's
+    colour.  names: the class names (bytes or ASCII str, at most 16 bytes each), names[c] for an NMS box of class c ('class' mode)
+    and for the top-1 box the class of `pose`.  The call then also takes pose=(N,4) float32 [azimuth, radius, depth, class] of
+    Detector.pose_device -- the top-1 label's name and, with show_azimuth, its azimuth in degrees -- and nms_scores=(N,post_nms)
+    float32, the kept scores of Detector.nms / decode_nms (without them an NMS label shows its row's column 0).  `.labels` is the
+    label table of the last call (include/yolo_amd.h, yolo_overlay_labels).  With labels=False nothing changes."""
 
     def __init__(self, camera=None, car_threshold=0.5, LP_threshold=0.5, thickness=2, use_r=False, car_color=PALETTE[4],
-                 LP_color=(0, 0, 255), palette=PALETTE, LP_size=(160, 380), device='cuda:0'):
+                 LP_color=(0, 0, 255), palette=PALETTE, LP_size=(160, 380), device='cuda:0', labels=False, names=None, font=None,
+                 font_scale=1, label_gap=4, label_pad=1, label_ground=(0, 0, 0), show_azimuth=True):
         import torch
         from . import render
         if camera is not None and not isinstance(camera, render.PlateCamera):
@@ -72,7 +137,29 @@ class FrameOverlay(object):
         self._shape = {}                  # (N, K) -> (table, vertices)
         self._plate = {}                  # N -> (matrices, lp_valid)
         self._clip = {}                   # (N, C) -> clipped
-        self.table = self.vertices = self.matrices = None
+        self.table = self.vertices = self.matrices = self.labels = None
+        self.with_labels = bool(labels)
+        if self.with_labels:
+            if font is None:
+                font = default_font()
+            if not isinstance(font, BitmapFont):
+                raise ValueError('font should be a BitmapFont')
+            self.font = font
+            self._font = torch.from_numpy(font.masks.view(np.int32)).to(self.device)
+            self.font_scale, self.label_gap, self.label_pad = int(font_scale), int(label_gap), int(label_pad)
+            if not 1 <= self.font_scale <= 16 or self.label_gap < 0 or self.label_pad < 0:
+                raise ValueError('font_scale should be in 1..16, label_gap and label_pad not negative')
+            self._ground = 0 if label_ground is None else 1
+            self._ground_colour = 0 if label_ground is None else _pack(label_ground)
+            self.show_azimuth = bool(show_azimuth)
+            table = np.zeros((len(names) if names is not None else 0, NAME_BYTES), np.uint8)
+            for k in range(table.shape[0]):
+                raw = names[k].encode('ascii') if isinstance(names[k], str) else bytes(names[k])
+                if len(raw) > NAME_BYTES or 0 in raw:
+                    raise ValueError('a class name is at most %d bytes without a zero byte: %r' % (NAME_BYTES, names[k]))
+                table[k, :len(raw)] = np.frombuffer(raw, np.uint8)
+            self._names = torch.from_numpy(table).to(self.device) if table.shape[0] else None
+            self._label = {}              # (N, K) -> labels
 
     def _rows(self, t, name, width, N):
         import torch
@@ -81,7 +168,7 @@ class FrameOverlay(object):
             raise ValueError('%s should be a contiguous float32 tensor (%d, >=%d) on %s' % (name, N, width, self.device))
         return t
 
-    def __call__(self, frames, pred=None, lp=None, nms=None, out=None, nms_mode='class'):
+    def __call__(self, frames, pred=None, lp=None, nms=None, out=None, nms_mode='class', pose=None, nms_scores=None):
         import torch
         L.require_current_device(self.device, 'this FrameOverlay')
         if (not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.device != self.device or frames.dim() != 4
@@ -143,6 +230,20 @@ class FrameOverlay(object):
             clipped = self._clip.get((N, Cc))
             if clipped is None:
                 clipped = self._clip[(N, Cc)] = torch.empty((N, Cc) + self.LP_size, dtype=torch.float32, device=self.device)
+        labels = None
+        if self.with_labels:
+            if pose is not None and (pred is None or not torch.is_tensor(pose) or pose.dtype != torch.float32
+                                     or pose.device != self.device or tuple(pose.shape) != (N, 4) or not pose.is_contiguous()):
+                raise ValueError('pose should be a contiguous float32 tensor (%d, 4) on %s, given with pred' % (N, self.device))
+            if nms_scores is not None and (nms is None or not torch.is_tensor(nms_scores) or nms_scores.dtype != torch.float32
+                                           or nms_scores.device != self.device or tuple(nms_scores.shape) != (N, post)
+                                           or not nms_scores.is_contiguous()):
+                raise ValueError('nms_scores should be a contiguous float32 tensor (%d, post_nms) on %s, given with nms' % (N, self.device))
+            labels = self._label.get((N, K))
+            if labels is None:
+                labels = self._label[(N, K)] = torch.empty((N, K, LABEL_WORDS), dtype=torch.int32, device=self.device)
+        elif pose is not None or nms_scores is not None:
+            raise ValueError('pose and nms_scores are for the text labels: FrameOverlay(labels=True)')
         stream = L.stream_ptr()
         L.check(self._lib.yolo_overlay_shapes(
             L.ptr(rows), L.ptr(kept), L.ptr(count), nbox, rows_C, post, cpb, L.ptr(self._palette), int(self._palette.shape[0]),
@@ -150,6 +251,13 @@ class FrameOverlay(object):
             L.ptr(lp), cam.fx if cam else 0.0, cam.fy if cam else 0.0, cam.cx if cam else 0.0, cam.cy if cam else 0.0,
             cam.w if cam else 0, cam.h if cam else 0, self.LP_threshold, self._lp, self.LP_size[0], self.LP_size[1],
             N, H, W, self.thickness, L.ptr(table), K, L.ptr(verts), L.ptr(mats), L.ptr(valid), stream), 'overlay_shapes')
+        if labels is not None:
+            f = self.font
+            L.check(self._lib.yolo_overlay_labels(
+                L.ptr(table), L.ptr(rows), L.ptr(kept), L.ptr(count), L.ptr(nms_scores), nbox, rows_C, post, cpb, L.ptr(pred), pred_C,
+                L.ptr(pose), int(self.show_azimuth), L.ptr(lp), L.ptr(self._names), 0 if self._names is None else int(self._names.shape[0]),
+                f.cell_w, f.cell_h, f.advance, self.font_scale, self.label_gap, self.label_pad, self._ground, self._ground_colour,
+                N, H, W, K, L.ptr(labels), stream), 'overlay_labels')
         if lp is not None:
             # the same call rectify_plates makes (border 0), with the device-made matrices, on the frames as they came
             L.check(self._lib.yolo_warp_u8_to_nchw(L.ptr(frames), L.ptr(clipped), L.ptr(mats), None, N, H, W, Cc, self.LP_size[0],
@@ -158,5 +266,10 @@ class FrameOverlay(object):
             out.copy_(frames)
             frames = out
         L.check(self._lib.yolo_overlay_draw(L.ptr(frames), L.ptr(table), N, H, W, Cc, K, stream), 'overlay_draw')
-        self.table, self.vertices, self.matrices = table, verts, mats
+        if labels is not None:
+            # after the draw and after the clipped plate was read: the text lies over every shape and never reaches `clipped`
+            f = self.font
+            L.check(self._lib.yolo_overlay_text(L.ptr(frames), L.ptr(labels), L.ptr(self._font), f.nglyph, f.first_code, f.cell_w, f.cell_h,
+                                                f.advance, self.font_scale, self.label_pad, N, H, W, Cc, K, stream), 'overlay_text')
+        self.table, self.vertices, self.matrices, self.labels = table, verts, mats, labels
         return frames, clipped, valid
