@@ -184,7 +184,7 @@ def test_stem_kernels(lib, cuda, shape, dtype):
 
 
 @pytest.mark.parametrize('dtype', ['bf16', 'f16'])
-@pytest.mark.parametrize('case', [(3, 5, 62, 64), (1, 33, 63, 64), (1, 40, 8, 128)])
+@pytest.mark.parametrize('case', [(3, 5, 62, 64), (1, 33, 63, 64), (1, 40, 8, 128), (1, 21, 66, 128)])
 def test_res_block(lib, cuda, case, dtype):
     """yolo_res_block_fwd against the torch reference with the HIP path's rounding points (test_res_block_fused's bars)."""
     ldt, tdt, sim = LDT[dtype], TDT[dtype], (True if dtype == 'bf16' else 'f16')

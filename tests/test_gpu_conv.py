@@ -344,7 +344,7 @@ def test_conv_pipe_1x1_short_k(lib, cuda, algo, cin):
 
 @pytest.mark.parametrize('dtype', ['bf16', 'f16'])
 @pytest.mark.parametrize('case', [(2, 37, 70, 64), (1, 20, 130, 128), (3, 5, 62, 64), (1, 40, 8, 128), (2, 52, 104, 128),
-                                  (1, 33, 63, 64), (1, 64, 208, 64)])
+                                  (1, 33, 63, 64), (1, 64, 208, 64), (1, 21, 66, 128)])
 def test_res_block_fused(lib, cuda, case, dtype):
     """yolo_res_block_fwd (one DarknetBasicBlockV3 of the first stages as one kernel) against the torch reference on the
     bf16-rounded operands with the HIP path's rounding points, and against the two separate HIP layers: several strips

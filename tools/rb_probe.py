@@ -1,4 +1,4 @@
-"""Time yolo_res_block_fwd on one shape (ablation bits via YOLO_RB_AB)."""
+"""Time yolo_res_block_fwd on one shape: python tools/rb_probe.py N H W C  (no knob: point YOLO_AMD_LIB at another build for an A/B)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -25,4 +25,4 @@ e0.record()
 for _ in range(20): run()
 e1.record(); torch.cuda.synchronize()
 us = e0.elapsed_time(e1) * 1e3 / 20
-print('ab=%s  %dx%dx%dx%d  %.1f us  (%.2f TB/s of read+write once)' % (os.environ.get('YOLO_RB_AB', '0'), N, H, W, C, us, 2 * x.numel() * 2 / us / 1e6))
+print('%dx%dx%dx%d  %.1f us  (%.2f TB/s of read+write once)' % (N, H, W, C, us, 2 * x.numel() * 2 / us / 1e6))

@@ -13,8 +13,8 @@
 // Same packed-weight image, operand order and rounding points as the other convolution kernels.
 #include "common.h"
 #include "conv_args.h"
+#include "row_walk.h"
 #include <stdio.h>
-#include <stdlib.h>
 #include <type_traits>
 
 struct StreamArgs {
@@ -42,11 +42,11 @@ __global__ __launch_bounds__(256) void conv_stream_kernel(StreamArgs a) {
     constexpr int INUSE = KS, NEW = S, RING = INUSE + NEW;
     constexpr int XROW = XW * PITCH;
     // stride 2: a ring row holds its even pixels first, then the odd ones -- the fragment reads (every other pixel) then have a lane
-    // stride of PITCH, an odd number of 16-byte units, instead of 2 * PITCH (two-way bank conflicts; stem_down.hip)
+    // stride of PITCH, an odd number of 16-byte units, instead of 2 * PITCH (two-way bank conflicts; row_walk.h)
     constexpr int XHALF = (XW + 1) / 2;
     auto pxoff = [](int px) { return S == 2 ? ((px & 1) * XHALF + (px >> 1)) * PITCH : px * PITCH; };
     constexpr int XU = (NEW * XW * PARTS + 255) / 256;
-    constexpr int SCR = 32 * 144;                        // per-wave epilogue scratch: 32 pixel rows x (32 f32 + pad)
+    constexpr int SCR = rw::SCR;                         // per-wave epilogue scratch
     __shared__ __attribute__((aligned(16))) char smem[RING * XROW + 4 * SCR];
     char* xl = smem;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -68,28 +68,15 @@ __global__ __launch_bounds__(256) void conv_stream_kernel(StreamArgs a) {
 
     // ---- the wave's weights: A-fragments of its 32 couts for every K-step, straight from the packed image ----
     uint4 A[KSTEPS];
-    {
-        const int row = wave_c * 32 + l31;
-        const int swz = (l31 >> 2) & 3;
-#pragma unroll
-        for (int ks = 0; ks < KSTEPS; ++ks) {
-            const int tap = ks / KC, kc = ks % KC;
-            const int chunk = kc >> 1, unit = ((kc & 1) * 2 + h) ^ swz;
-            A[ks] = *(const uint4*)(a.wp + ((long long)(chunk * NTAP + tap) * a.Cout_pad + row) * 64 + unit * 16);
-        }
-    }
+    rw::load_a_frags<KS, CIN>(A, a.wp, a.Cout_pad, wave_c * 32, lane);
     // ---- per-lane epilogue constants (after the transpose a lane owns 8 couts of a pixel row) -------------------
     const int ecol = lane & 3, erow0 = lane >> 2;
     const int eco = wave_c * 32 + ecol * 8;
     float sc[8], bi[8];
     const bool ident = a.scale == nullptr;               // identity epilogue (conv_epilogue.h)
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        f32x4 s4 = {1.f, 1.f, 1.f, 1.f}, b4 = {0.f, 0.f, 0.f, 0.f};
-        if (!ident) { s4 = *(const f32x4*)(a.scale + eco + 4 * q); b4 = *(const f32x4*)(a.bias + eco + 4 * q); }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { sc[4 * q + e] = s4[e]; bi[4 * q + e] = b4[e]; }
-    }
+    for (int e = 0; e < 8; ++e) { sc[e] = 1.f; bi[e] = 0.f; }
+    if (!ident) rw::load_bn_row(sc, bi, a.scale, a.bias, eco);
     const float slope = a.slope;
     const bool has_res = a.res != nullptr;
     float ssum[8], qsum[8];                              // STATS: sums of the stored values of this lane's 8 channels
@@ -201,21 +188,11 @@ __global__ __launch_bounds__(256) void conv_stream_kernel(StreamArgs a) {
         // ---- epilogue: folded BN, LeakyReLU, residual, one rounding, 16-byte row stores ---------------------------
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4 v = {acc[ni][4 * g], acc[ni][4 * g + 1], acc[ni][4 * g + 2], acc[ni][4 * g + 3]};
-                *(f32x4*)(scr + l31 * 144 + (8 * g + 4 * h) * 4) = v;
-            }
-            wave_lds_fence();
+            rw::scratch_put(scr, acc[ni], lane);
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 float v[8];
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const f32x4 t4 = *(const f32x4*)(scr + (erow0 + 16 * k) * 144 + (ecol * 8 + 4 * q) * 4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[4 * q + e] = t4[e];
-                }
+                rw::scratch_get(v, scr, lane, k);
                 if (!ident) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
@@ -223,17 +200,9 @@ __global__ __launch_bounds__(256) void conv_stream_kernel(StreamArgs a) {
                         v[e] = leaky(t, slope);
                     }
                 }
-                if (has_res) {
-                    const uint32_t w[4] = {rv[ni][k].x, rv[ni][k].y, rv[ni][k].z, rv[ni][k].w};
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        v[2 * q] += Elem<T>::lo(w[q]);
-                        v[2 * q + 1] += Elem<T>::hi(w[q]);
-                    }
-                }
+                if (has_res) rw::add8<T>(v, rv[ni][k]);
                 if (yo[ni][k] >= 0) {
-                    const uint4 o = make_uint4(Elem<T>::pack2(v[0], v[1]), Elem<T>::pack2(v[2], v[3]), Elem<T>::pack2(v[4], v[5]),
-                                               Elem<T>::pack2(v[6], v[7]));
+                    const uint4 o = rw::pack8<T>(v);
                     *(uint4*)(a.y + yo[ni][k]) = o;
                     if constexpr (STATS) {
                         const uint32_t ow[4] = {o.x, o.y, o.z, o.w};
@@ -284,8 +253,7 @@ static int launch_stream(const ConvArgs& c, hipStream_t st, const NameOut* nm) {
     a.x = c.x; a.wp = c.wp; a.scale = c.scale; a.bias = c.bias; a.res = c.res; a.y = c.y;
     a.N = c.N; a.H = c.H; a.W = c.W; a.Ho = c.Ho; a.Wo = c.Wo; a.Cout_pad = c.Cout_pad;
     a.slope = c.slope;
-    a.nstrips = (c.Wo + TW - 1) / TW;
-    a.strip_w = (c.Wo + a.nstrips - 1) / a.nstrips;              // balanced strips (<= TW)
+    rw::walker_strips(c.Wo, TW, a.nstrips, a.strip_w);
     const long long bx = (long long)c.N * a.nstrips;
     const long long target = 3072;                                // (768..12288 measured: flat within noise)
     long long slices = (target + bx - 1) / bx;                      // ~12 blocks per CU over the launch (several rounds: small tail)

@@ -14,25 +14,15 @@
 //   * stem pixels outside the image are written as zeros (they are the down conv's zero padding, NOT stem(padding)).
 // Same operand order, accumulation order and rounding points as the two separate kernels: results are bit-identical.
 #include "common.h"
-#include <stdio.h>
+#include "row_walk.h"
 #include <type_traits>
 
+using namespace rw;
+
 namespace {
-constexpr int C1 = 32, C2 = 64;
+constexpr int C1 = STEM_C, C2 = 64;
 // a step covers 64 output pixels (MFMA columns); the usable strip width is <= 62 so that a stem row is 4 groups of 32
 constexpr int SW_MAX = 62;
-constexpr int XW = 129;                  // stem ring row capacity (pixel 128 is only read by discarded lanes)
-constexpr int PITCH = C1 * 2 + 16;       // bytes per stem pixel in the ring (+16: conflict-free 16-byte reads)
-constexpr int XROW = XW * PITCH;
-// A ring row holds its even pixels first, then the odd ones (pixel p at ((p & 1) * XHALF + (p >> 1)) * PITCH): the stride-2 down conv
-// reads every other pixel, and at a lane stride of 2 * PITCH = 160 bytes a 16-lane ds_read_b128 group covers only 8 of the 16 bank
-// quads (two-way conflicts on every fragment read: SQ_LDS_BANK_CONFLICT was 34 % of the LDS-active cycles); at PITCH it covers all 16.
-constexpr int XHALF = (XW + 1) / 2;
-constexpr int RING = 5;                  // 3 stem rows in use + 2 being produced
-constexpr int IPW = 136;                 // image window row pitch in pixels (8 B each: NHWC4 bf16)
-constexpr int IROWS = 8;                 // image window rows (4 in use + 2 arriving, power of two)
-constexpr int SCR = 32 * 144;            // per-wave epilogue scratch
-constexpr int KSTEPS = 18;               // 9 taps x 2 k-steps of 16 channels
 
 struct Args {
     const float* x;
@@ -51,14 +41,13 @@ struct Args {
 
 template <typename T>
 __global__ __launch_bounds__(256) void stem_down_kernel(Args a) {
-    __shared__ __attribute__((aligned(16))) char smem[RING * XROW + IROWS * IPW * 8 + 4 * SCR];
+    __shared__ __attribute__((aligned(16))) char smem[RING * STEM_ROW + IROWS * IPW * 8 + 4 * SCR];
     char* xl = smem;
-    uint2* img = (uint2*)(smem + RING * XROW);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, h = lane >> 5;
     const int wave_c = wave & 1, wave_p = wave >> 1;
-    char* scr = smem + RING * XROW + IROWS * IPW * 8 + wave * SCR;
+    char* scr = smem + RING * STEM_ROW + IROWS * IPW * 8 + wave * SCR;
 
     const int strip = blockIdx.x % a.nstrips;
     const int n = blockIdx.x / a.nstrips;
@@ -67,102 +56,34 @@ __global__ __launch_bounds__(256) void stem_down_kernel(Args a) {
     const int oy0 = blockIdx.y * a.rows_per_slice;
     const int oy1 = min(oy0 + a.rows_per_slice, a.Ho);
     if (oy0 >= oy1) return;
-    const int H = a.H, W = a.W, Ho = a.Ho, Wo = a.Wo;
-    const long long HW = (long long)H * W;
-    const float* xn = a.x + (long long)n * 3 * HW;
-    const int sx0 = 2 * ox0 - 1;              // image column of stem pixel 0
-    const int icol0 = sx0 - 1;                // image column of window pixel 0
-    const int iyb = 2 * oy0 - 2;              // image row held in window slot 0 at the start
+    const int Ho = a.Ho, Wo = a.Wo;
+    StemWin sw;
+    sw.HW = (long long)a.H * a.W;
+    sw.xn = a.x + (long long)n * 3 * sw.HW;
+    sw.H = a.H; sw.W = a.W;
+    sw.sx0 = 2 * ox0 - 1;
+    sw.icol0 = sw.sx0 - 1;
+    sw.iyb = 2 * oy0 - 2;
+    sw.img = (uint2*)(smem + RING * STEM_ROW);
+    sw.ring = xl;
+    sw.tid = tid;
+    const int iyb = sw.iyb;
 
     // ---- hygiene: pixels of both LDS arrays that are never written are only read by discarded lanes ---------------
-    for (int i = tid; i < (RING * XROW + IROWS * IPW * 8) / 16; i += 256) ((uint4*)smem)[i] = make_uint4(0, 0, 0, 0);
+    for (int i = tid; i < (RING * STEM_ROW + IROWS * IPW * 8) / 16; i += 256) ((uint4*)smem)[i] = make_uint4(0, 0, 0, 0);
 
-    // ---- down conv: the wave's A-fragments (32 couts x K = 288) from the packed image, as conv_stream does --------
-    uint4 A[KSTEPS];
-    {
-        const int row = wave_c * 32 + l31;
-        const int swz = (l31 >> 2) & 3;
-#pragma unroll
-        for (int ks = 0; ks < KSTEPS; ++ks) {
-            const int tap = ks >> 1, kc = ks & 1;
-            const int unit = (kc * 2 + h) ^ swz;
-            A[ks] = *(const uint4*)(a.wp2 + ((long long)tap * a.Cout_pad2 + row) * 64 + unit * 16);
-        }
-    }
-    // ---- stem: weight fragments (cout = l31, k-half h), one per kernel row (stem.hip's K order) -------------------
+    // ---- the wave's weights and folded-BN constants: down conv (32 couts x K = 288; after the transpose), stem (MFMA layout) ----
+    uint4 A[18];
+    load_a_frags<3, C1>(A, a.wp2, a.Cout_pad2, wave_c * 32, lane);
     uint4 wf[3];
-#pragma unroll
-    for (int kh = 0; kh < 3; ++kh) {
-        float v[2][3];
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-            for (int ci = 0; ci < 3; ++ci) {
-                const int kw = 2 * h + q;          // h=0: kw 0,1 ; h=1: kw 2,(3 = padding)
-                v[q][ci] = kw < 3 ? a.w1[((l31 * 3 + ci) * 3 + kh) * 3 + min(kw, 2)] : 0.f;
-            }
-        wf[kh] = make_uint4(Elem<T>::pack2(v[0][0], v[0][1]), Elem<T>::pack2(v[0][2], 0.f), Elem<T>::pack2(v[1][0], v[1][1]),
-                            Elem<T>::pack2(v[1][2], 0.f));
-    }
-    // ---- epilogue constants of the down conv (after the transpose a lane owns 8 couts of a pixel row) -------------
+    stem_weight_frags<T>(wf, a.w1, lane);
     const int ecol = lane & 3, erow0 = lane >> 2;
     const int eco = wave_c * 32 + ecol * 8;
     float sc2[8], bi2[8];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const f32x4 s4 = *(const f32x4*)(a.scale2 + eco + 4 * q);
-        const f32x4 b4 = *(const f32x4*)(a.bias2 + eco + 4 * q);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { sc2[4 * q + e] = s4[e]; bi2[4 * q + e] = b4[e]; }
-    }
+    load_bn_row(sc2, bi2, a.scale2, a.bias2, eco);
     const float slope = a.slope;
-    // folded BN of the stem for the 16 couts a lane holds after its MFMAs (rows 8g + 4h + e)
     float sc1[16], bi1[16];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const f32x4 s4 = *(const f32x4*)(a.scale1 + 8 * g + 4 * h), b4 = *(const f32x4*)(a.bias1 + 8 * g + 4 * h);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { sc1[4 * g + e] = s4[e]; bi1[4 * g + e] = b4[e]; }
-    }
-
-    // ---- image window: one pixel (3 planes) per thread per pass; rows [first, first+nrows) -------------------------
-    auto load_img = [&](int iy_first, int r, float (&c)[3], bool& ok) {
-        const int q = tid & 127;
-        const int iy = iy_first + r * 2 + (tid >> 7), ix = icol0 + q;
-        ok = iy >= 0 && iy < H && ix >= 0 && ix < W;
-        const long long o = (long long)min(max(iy, 0), H - 1) * W + min(max(ix, 0), W - 1);
-        c[0] = xn[o]; c[1] = xn[HW + o]; c[2] = xn[2 * HW + o];
-    };
-    auto store_img = [&](int iy_first, int r, const float (&c)[3], bool ok) {
-        const int q = tid & 127;
-        const int iy = iy_first + r * 2 + (tid >> 7);
-        img[((iy - iyb) & (IROWS - 1)) * IPW + q] =
-            ok ? make_uint2(Elem<T>::pack2(c[0], c[1]), Elem<T>::pack2(c[2], 0.f)) : make_uint2(0u, 0u);
-    };
-    // ---- one group of 32 stem pixels of stem row sy: 3 MFMAs, BN + LeakyReLU, one rounding, into ring slot `slot` --
-    auto stem_group = [&](int sy, int slot, int pxg) {
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-            const int s = ((sy - 1 + kh - iyb) & (IROWS - 1)) * IPW + pxg * 32 + l31 + 2 * h;
-            const uint2 lo = img[s], hi = img[s + 1];
-            acc = mfma16<T>(wf[kh], make_uint4(lo.x, lo.y, hi.x, hi.y), acc);
-        }
-        const int px = pxg * 32 + l31;
-        const int sx = sx0 + px;
-        const bool inside = sy >= 0 && sy < H && sx >= 0 && sx < W;
-        char* dst = xl + slot * XROW + ((px & 1) * XHALF + (px >> 1)) * PITCH;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int co = 8 * g + 4 * h;
-            float v[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = leaky(acc[4 * g + e] * sc1[4 * g + e] + bi1[4 * g + e], slope);
-            *(uint2*)(dst + co * 2) = inside ? make_uint2(Elem<T>::pack2(v[0], v[1]), Elem<T>::pack2(v[2], v[3])) : make_uint2(0u, 0u);
-        }
-    };
+    load_bn_mfma(sc1, bi1, a.scale1, a.bias1, 0, h);
 
     __syncthreads();                                        // the zero fill
     // ---- prologue: image rows iyb .. iyb+6, then stem rows 2 oy0 - 1 .. 2 oy0 + 1 into ring slots 0..2 ------------
@@ -170,30 +91,27 @@ __global__ __launch_bounds__(256) void stem_down_kernel(Args a) {
         float c[4][3];
         bool ok[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) load_img(iyb, r, c[r], ok[r]);
+        for (int r = 0; r < 4; ++r) load_img(sw, iyb, r, c[r], ok[r]);
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-            if (r < 3 || tid < 128) store_img(iyb, r, c[r], ok[r]);      // 7 rows: the 8th slot belongs to row iyb + 7
+            if (r < 3 || tid < 128) store_img<T>(sw, iyb, r, c[r], ok[r]);      // 7 rows: the 8th slot belongs to row iyb + 7
     }
     __syncthreads();
 #pragma unroll
-    for (int r = 0; r < 3; ++r) stem_group(2 * oy0 - 1 + r, r, wave);
+    for (int r = 0; r < 3; ++r) stem_group<T>(sw, wf, sc1, bi1, slope, lane, 2 * oy0 - 1 + r, r, wave);
     __syncthreads();
 
-    const int b_off = (wave_p * 32 + l31) * PITCH + h * 16;          // (pixel 2 j + kw: half kw & 1, index j + (kw >> 1))
+    const int b_off = (wave_p * 32 + l31) * PITCH + h * 16;
     int slot0 = 0;
     // image rows 2oy+5, 2oy+6 are used by step oy+1's stem rows and stored at the bottom of step oy; they are requested TWO
-    // steps ahead (top of step oy-1) into one of two register sets, unconditionally (clamped addresses: always readable) --
-    // a uniform branch around the request would make the compiler wait for every load in flight before the other set's store
+    // steps ahead (top of step oy-1) into one of two register sets (load_img)
     float cimg[2][3];
     bool okimg[2] = {false, false};
-    load_img(2 * oy0 + 5, 0, cimg[0], okimg[0]);
+    load_img(sw, 2 * oy0 + 5, 0, cimg[0], okimg[0]);
     auto step = [&](auto par_c, int oy) {
         constexpr int PAR = decltype(par_c)::value;
         const bool more = oy + 1 < oy1;
-        load_img(2 * oy + 7, 0, cimg[PAR ^ 1], okimg[PAR ^ 1]);
-        float (&c)[3] = cimg[PAR];
-        const bool ok = okimg[PAR];
+        load_img(sw, 2 * oy + 7, 0, cimg[PAR ^ 1], okimg[PAR ^ 1]);
         long long yo[2];
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
@@ -201,54 +119,25 @@ __global__ __launch_bounds__(256) void stem_down_kernel(Args a) {
             yo[k] = ox < ox_end ? ((((long long)n * Ho + oy) * Wo + ox) * C2 + eco) * 2 : -1;
         }
         // ---- down conv of output row oy: 9 taps x 2 k-steps over the stem ring ----------------------------------
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
+        f32x16 acc[1];
+        conv3x3_rows<T, 2, 1, PITCH>(acc, A, [&](int kh) {
             int slot = slot0 + kh;
             if (slot >= RING) slot -= RING;
-            const char* rowp = xl + slot * XROW + b_off;
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw)
-#pragma unroll
-                for (int kc = 0; kc < 2; ++kc) {
-                    const uint4 bf = *(const uint4*)(rowp + ((kw & 1) * XHALF + (kw >> 1)) * PITCH + kc * 32);
-                    acc = mfma16<T>(A[(kh * 3 + kw) * 2 + kc], bf, acc);
-                }
-        }
+            return xl + slot * STEM_ROW + b_off;
+        }, TapS2{});
         // ---- the two stem rows the next output row adds (2oy+2, 2oy+3): this wave's pixel group of each ----------
         if (more) {
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
                 int slot = slot0 + 3 + r;
                 if (slot >= RING) slot -= RING;
-                stem_group(2 * oy + 2 + r, slot, wave);
+                stem_group<T>(sw, wf, sc1, bi1, slope, lane, 2 * oy + 2 + r, slot, wave);
             }
         }
         // ---- epilogue of the down conv: folded BN, LeakyReLU, one rounding, 16-byte row stores --------------------
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4 v = {acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
-            *(f32x4*)(scr + l31 * 144 + (8 * g + 4 * h) * 4) = v;
-        }
-        wave_lds_fence();
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            float v[8];
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const f32x4 t4 = *(const f32x4*)(scr + (erow0 + 16 * k) * 144 + (ecol * 8 + 4 * q) * 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[4 * q + e] = t4[e];
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = leaky(v[e] * sc2[e] + bi2[e], slope);
-            if (yo[k] >= 0)
-                *(uint4*)(a.y + yo[k]) = make_uint4(Elem<T>::pack2(v[0], v[1]), Elem<T>::pack2(v[2], v[3]),
-                                                    Elem<T>::pack2(v[4], v[5]), Elem<T>::pack2(v[6], v[7]));
-        }
-        if (more) store_img(2 * oy + 5, 0, c, ok);
+        row_epilogue<T>(scr, acc[0], lane, sc2, bi2, slope, [](int) { return NoResidual{}; },
+                        [&](int k, const uint4& o) { if (yo[k] >= 0) *(uint4*)(a.y + yo[k]) = o; });
+        if (more) store_img<T>(sw, 2 * oy + 5, 0, cimg[PAR], okimg[PAR]);
         slot0 += 2;
         if (slot0 >= RING) slot0 -= RING;
         __syncthreads();
@@ -274,8 +163,7 @@ extern "C" int yolo_stem_down_fwd(const float* x_nchw, const float* w1_oihw, con
     a.N = N; a.H = H; a.W = W; a.Ho = (H - 1) / 2 + 1; a.Wo = (W - 1) / 2 + 1;
     a.Cout_pad2 = round_up(C2, YOLO_COUT_PAD);
     a.slope = slope;
-    a.nstrips = (a.Wo + SW_MAX - 1) / SW_MAX;
-    a.strip_w = (a.Wo + a.nstrips - 1) / a.nstrips;
+    walker_strips(a.Wo, SW_MAX, a.nstrips, a.strip_w);
     const long long bx = (long long)N * a.nstrips;
     if (bx > 0x7fffffffLL) return YOLO_EUNSUPPORTED;
     long long slices = (1536 + bx - 1) / bx;                 // a slice re-computes 3 stem rows: keep them >= 16 rows

@@ -24,26 +24,19 @@
 // Same operand order, K order, accumulation order and rounding points as yolo_stem_down_fwd followed by yolo_res_block_fwd:
 // results are bit-identical.
 #include "common.h"
+#include "row_walk.h"
 #include <type_traits>
 
+using namespace rw;
+
 namespace {
-constexpr int C1 = 32, C = 64;
+constexpr int C1 = STEM_C, C = 64;
 constexpr int SW_MAX = 60;               // consumer strip width: + 2 halo columns = the producer's 62
-// ---- producer (stem_down.hip's constants) -------------------------------------------------------------------------------
-constexpr int XW = 129;                  // stem ring row capacity (pixel 128 is only read by discarded lanes)
-constexpr int PITCH = C1 * 2 + 16;       // bytes per stem pixel
-constexpr int SROW = XW * PITCH;
-constexpr int XHALF = (XW + 1) / 2;      // a stem ring row holds its even pixels first, then the odd ones
-constexpr int RING = 5;                  // 3 stem rows in use + 2 being produced
-constexpr int IPW = 136;                 // image window row pitch in pixels (8 B each)
-constexpr int IROWS = 8;
-// ---- consumer (res_block.hip's constants at C = 64) -------------------------------------------------------------------------
-constexpr int MW = 64;
+// ---- consumer (res_block_kernel<64>'s rings) ----------------------------------------------------------------------------
 constexpr int PX = C * 2 + 16, PM = C1 * 2 + 16;
 constexpr int XROW = MW * PX, MROW = (MW + 2) * PM;
-constexpr int SCR = 32 * 144;            // per-wave epilogue scratch of the consumer
-// ---- LDS map ----------------------------------------------------------------------------------------------------------------
-constexpr int OFF_IMG = RING * SROW;
+// ---- LDS map: the producer's stem ring and image window (row_walk.h), the two rings of the consumer, its scratch -------------
+constexpr int OFF_IMG = RING * STEM_ROW;
 constexpr int OFF_X = OFF_IMG + IROWS * IPW * 8;
 constexpr int XSLOTS = 4, MSLOTS = 4;   // rows oy .. oy+3 of the input ring, oy-1 .. oy+2 of the mid ring are live in step oy
 constexpr int OFF_M = OFF_X + XSLOTS * XROW;
@@ -80,8 +73,6 @@ struct SRGeom { int nstrips, strip_w, rows_per_slice, slices; long long bx; };
 template <typename T>
 __global__ __launch_bounds__(512) void stem_res_kernel(SRArgs a) {
     __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
-    char* sl = smem;                                         // stem ring
-    uint2* img = (uint2*)(smem + OFF_IMG);                   // image window
     char* xl = smem + OFF_X;                                 // the consumer's input ring = the producer's output
     char* ml = smem + OFF_M;                                 // mid ring
     const int tid = threadIdx.x & 255, lane = tid & 63;      // thread / wave index inside the role group
@@ -99,255 +90,102 @@ __global__ __launch_bounds__(512) void stem_res_kernel(SRArgs a) {
     const int oy0 = blockIdx.y * a.rows_per_slice;
     const int oy1 = min(oy0 + a.rows_per_slice, a.Ho);
     if (oy0 >= oy1) return;                                  // (the whole block, before its first barrier)
-    const int H = a.H, W = a.W, Ho = a.Ho, Wo = a.Wo;
-    const long long HW = (long long)H * W;
-    const float* xn = a.x + (long long)n * 3 * HW;
+    const int Ho = a.Ho, Wo = a.Wo;
     const int mx0 = ox0 - 1;                  // map column of ring pixel 0 (= the producer's first output column)
-    const int sx0 = 2 * mx0 - 1;              // image column of stem pixel 0
-    const int icol0 = sx0 - 1;                // image column of window pixel 0
     const int pr0 = oy0 - 1;                  // the producer's first row
-    const int iyb = 2 * pr0 - 2;              // image row held in window slot 0 at the start
+    StemWin sw;
+    sw.HW = (long long)a.H * a.W;
+    sw.xn = a.x + (long long)n * 3 * sw.HW;
+    sw.H = a.H; sw.W = a.W;
+    sw.sx0 = 2 * mx0 - 1;
+    sw.icol0 = sw.sx0 - 1;
+    sw.iyb = 2 * pr0 - 2;
+    sw.img = (uint2*)(smem + OFF_IMG);
+    sw.ring = smem;
+    sw.tid = tid;
+    const int iyb = sw.iyb;
 
     // ---- hygiene: pixels of the LDS arrays that are never written are only read by discarded lanes ---------------------
     for (int i = threadIdx.x; i < OFF_SCR / 16; i += 512) ((uint4*)smem)[i] = make_uint4(0, 0, 0, 0);
 
-    // ---- the role's 3x3 weights: 18 A-fragments (32 couts x K = 288) from the packed image, conv_stream's addressing ----------
-    const int swz = (l31 >> 2) & 3;
+    // ---- the role's weights and folded-BN constants, in the same registers for both roles -----------------------------------
+    // 3x3: 18 A-fragments (32 couts x K = 288), down conv | the block's 3x3
     uint4 A[18];
-    {
-        const char* wp = prod ? a.wpd : a.wp2;
-        const int row = wave_c * 32 + l31;
-#pragma unroll
-        for (int ks = 0; ks < 18; ++ks) {
-            const int tap = ks >> 1, kc = ks & 1;
-            const int unit = (kc * 2 + h) ^ swz;
-            A[ks] = *(const uint4*)(wp + ((long long)tap * a.Cpad + row) * 64 + unit * 16);
-        }
-    }
-    // ---- the role's small conv: the stem's 3 weight fragments (one per kernel row) | the 1x1's 4 A-fragments ---------------
+    load_a_frags<3, C1>(A, prod ? a.wpd : a.wp2, a.Cpad, wave_c * 32, lane);
+    // small conv: the stem's 3 weight fragments (one per kernel row) | the 1x1's 4 A-fragments, and its BN in the MFMA layout
     uint4 ws[4];
     if (prod) {
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-            float v[2][3];
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-#pragma unroll
-                for (int ci = 0; ci < 3; ++ci) {
-                    const int kw = 2 * h + q;          // h=0: kw 0,1 ; h=1: kw 2,(3 = padding)
-                    v[q][ci] = kw < 3 ? a.w0[((l31 * 3 + ci) * 3 + kh) * 3 + min(kw, 2)] : 0.f;
-                }
-            ws[kh] = make_uint4(Elem<T>::pack2(v[0][0], v[0][1]), Elem<T>::pack2(v[0][2], 0.f), Elem<T>::pack2(v[1][0], v[1][1]),
-                                Elem<T>::pack2(v[1][2], 0.f));
-        }
+        stem_weight_frags<T>(ws, a.w0, lane);
         ws[3] = make_uint4(0, 0, 0, 0);
     } else {
-#pragma unroll
-        for (int kc = 0; kc < 4; ++kc) {
-            const int chunk = kc >> 1, unit = ((kc & 1) * 2 + h) ^ swz;
-            ws[kc] = *(const uint4*)(a.wp1 + ((long long)chunk * a.Cpad + l31) * 64 + unit * 16);
-        }
+        load_a_frags<1, C>(ws, a.wp1, a.Cpad, 0, lane);
     }
-    // folded BN of the small conv for the 16 couts a lane holds after its MFMAs (rows 8g + 4h + e): stem | 1x1
     float sc1[16], bi1[16];
-    {
-        const float* s = prod ? a.scale0 : a.scale1;
-        const float* b = prod ? a.bias0 : a.bias1;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 s4 = *(const f32x4*)(s + 8 * g + 4 * h), b4 = *(const f32x4*)(b + 8 * g + 4 * h);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { sc1[4 * g + e] = s4[e]; bi1[4 * g + e] = b4[e]; }
-        }
-    }
+    load_bn_mfma(sc1, bi1, prod ? a.scale0 : a.scale1, prod ? a.bias0 : a.bias1, 0, h);
     // folded BN of the 3x3.  Producer: the 16 couts of the MFMA layout (it writes the ring without a transpose); consumer:
     // the 8 couts of a pixel row a lane owns after the transpose (entries 0..7)
-    const int ecol = lane & 3, erow0 = lane >> 2;
-    const int eco = wave_c * 32 + ecol * 8;
+    const int eco = wave_c * 32 + (lane & 3) * 8;
     float sc2[16], bi2[16];
     if (prod) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 s4 = *(const f32x4*)(a.scaled + wave_c * 32 + 8 * g + 4 * h);
-            const f32x4 b4 = *(const f32x4*)(a.biasd + wave_c * 32 + 8 * g + 4 * h);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { sc2[4 * g + e] = s4[e]; bi2[4 * g + e] = b4[e]; }
-        }
+        load_bn_mfma(sc2, bi2, a.scaled, a.biasd, wave_c * 32, h);
     } else {
+        load_bn_row(sc2, bi2, a.scale2, a.bias2, eco);
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const f32x4 s4 = *(const f32x4*)(a.scale2 + eco + 4 * q), b4 = *(const f32x4*)(a.bias2 + eco + 4 * q);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { sc2[4 * q + e] = s4[e]; bi2[4 * q + e] = b4[e]; sc2[8 + 4 * q + e] = 0.f; bi2[8 + 4 * q + e] = 0.f; }
-        }
+        for (int e = 8; e < 16; ++e) sc2[e] = bi2[e] = 0.f;
     }
     const float slope = a.slope;
     auto slot4 = [](int row) { return (row + 4) & 3; };       // rows >= -1 (both rings have four slots)
 
-    // ==== producer pieces (stem_down_kernel's, with the output row going to the ring) ==========================================
-    // image window: one pixel (3 planes) per thread per pass; rows [first, first+nrows)
-    auto load_img = [&](int iy_first, int r, float (&c)[3], bool& ok) {
-        const int q = tid & 127;
-        const int iy = iy_first + r * 2 + (tid >> 7), ix = icol0 + q;
-        ok = iy >= 0 && iy < H && ix >= 0 && ix < W;
-        const long long o = (long long)min(max(iy, 0), H - 1) * W + min(max(ix, 0), W - 1);
-        c[0] = xn[o]; c[1] = xn[HW + o]; c[2] = xn[2 * HW + o];
-    };
-    auto store_img = [&](int iy_first, int r, const float (&c)[3], bool ok) {
-        const int q = tid & 127;
-        const int iy = iy_first + r * 2 + (tid >> 7);
-        img[((iy - iyb) & (IROWS - 1)) * IPW + q] =
-            ok ? make_uint2(Elem<T>::pack2(c[0], c[1]), Elem<T>::pack2(c[2], 0.f)) : make_uint2(0u, 0u);
-    };
-    // one group of 32 stem pixels of stem row sy: 3 MFMAs, BN + LeakyReLU, one rounding, into stem ring slot `slot`
-    auto stem_group = [&](int sy, int slot, int pxg) {
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-            const int s = ((sy - 1 + kh - iyb) & (IROWS - 1)) * IPW + pxg * 32 + l31 + 2 * h;
-            const uint2 lo = img[s], hi = img[s + 1];
-            acc = mfma16<T>(ws[kh], make_uint4(lo.x, lo.y, hi.x, hi.y), acc);
-        }
-        const int px = pxg * 32 + l31;
-        const int sx = sx0 + px;
-        const bool inside = sy >= 0 && sy < H && sx >= 0 && sx < W;
-        char* dst = sl + slot * SROW + ((px & 1) * XHALF + (px >> 1)) * PITCH;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int co = 8 * g + 4 * h;
-            float v[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = leaky(acc[4 * g + e] * sc1[4 * g + e] + bi1[4 * g + e], slope);
-            *(uint2*)(dst + co * 2) = inside ? make_uint2(Elem<T>::pack2(v[0], v[1]), Elem<T>::pack2(v[2], v[3])) : make_uint2(0u, 0u);
-        }
-    };
+    // ==== producer: stem_down_kernel's row step, with the output row going to the ring ==========================================
     const int b_off = (wave_p * 32 + l31) * PITCH + h * 16;
     int slot0 = 0;                                           // stem ring slot of stem row 2 R - 1
     float cimg[2][3];
     bool okimg[2] = {false, false};
-    // ring row R: request the image rows of two steps ahead (unconditional, clamped addresses: see stem_down.hip), the down conv
-    // of row R (9 taps x 2 k-steps over the stem ring), the two stem rows row R + 1 adds, the down conv's epilogue (folded BN,
-    // LeakyReLU, one rounding) into ring slot R % 4 -- zeros outside the map: the consumer's padding --, the image window rows of
-    // the next step
+    // ring row R: request the image rows of two steps ahead (load_img), the down conv of row R (9 taps x 2 k-steps over the stem
+    // ring), the two stem rows row R + 1 adds, the down conv's epilogue (folded BN, LeakyReLU, one rounding) into ring slot R % 4
+    // straight from the MFMA layout -- zeros outside the map: the consumer's padding --, the image window rows of the next step
     auto prod_row = [&](auto par_c, int R) {
         constexpr int PAR = decltype(par_c)::value;
-        load_img(2 * R + 7, 0, cimg[PAR ^ 1], okimg[PAR ^ 1]);
-        f32x16 pacc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) pacc[r] = 0.f;
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
+        load_img(sw, 2 * R + 7, 0, cimg[PAR ^ 1], okimg[PAR ^ 1]);
+        f32x16 pacc[1];
+        conv3x3_rows<T, 2, 1, PITCH>(pacc, A, [&](int kh) {
             int slot = slot0 + kh;
             if (slot >= RING) slot -= RING;
-            const char* rowp = sl + slot * SROW + b_off;
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw)
-#pragma unroll
-                for (int kc = 0; kc < 2; ++kc) {
-                    const uint4 bf = *(const uint4*)(rowp + ((kw & 1) * XHALF + (kw >> 1)) * PITCH + kc * 32);
-                    pacc = mfma16<T>(A[(kh * 3 + kw) * 2 + kc], bf, pacc);
-                }
-        }
+            return smem + slot * STEM_ROW + b_off;
+        }, TapS2{});
         const bool more = R < oy1;                           // (the producer's last row is oy1)
         if (more) {
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
                 int slot = slot0 + 3 + r;
                 if (slot >= RING) slot -= RING;
-                stem_group(2 * R + 2 + r, slot, wave);
+                stem_group<T>(sw, ws, sc1, bi1, slope, lane, 2 * R + 2 + r, slot, wave);
             }
         }
         const int j = wave_p * 32 + l31;
         const int col = mx0 + j;
-        const bool inside = R >= 0 && R < Ho && col >= 0 && col < Wo;
-        char* dst = xl + slot4(R) * XROW + j * PX + (wave_c * 32 + 4 * h) * 2;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float v[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = leaky(pacc[4 * g + e] * sc2[4 * g + e] + bi2[4 * g + e], slope);
-            *(uint2*)(dst + 16 * g) = inside ? make_uint2(Elem<T>::pack2(v[0], v[1]), Elem<T>::pack2(v[2], v[3])) : make_uint2(0u, 0u);
-        }
-        if (more) store_img(2 * R + 5, 0, cimg[PAR], okimg[PAR]);
+        store_tile<T>(xl + slot4(R) * XROW + j * PX + wave_c * 64, pacc[0], sc2, bi2, slope, h, R >= 0 && R < Ho && col >= 0 && col < Wo);
+        if (more) store_img<T>(sw, 2 * R + 5, 0, cimg[PAR], okimg[PAR]);
         slot0 += 2;
         if (slot0 >= RING) slot0 -= RING;
     };
 
-    // ==== consumer pieces (res_block_kernel<64>'s) ===============================================================================
-    // mid row my from the input ring: waves 0, 1 of the group make one 32-pixel tile each; zeros outside the image
+    // ==== consumer: res_block_kernel<64>'s row step, its input row and residual taken from the ring ==============================
+    // mid row my from the input ring: waves 0, 1 of the group make one 32-pixel tile each; zeros outside the map
     auto mid_row = [&](int my) {
         if (wave >= 2) return;
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        const char* xp = xl + slot4(my) * XROW + (wave * 32 + l31) * PX + h * 16;
-#pragma unroll
-        for (int kc = 0; kc < 4; ++kc) {
-            const uint4 bf = *(const uint4*)(xp + kc * 32);
-            acc = mfma16<T>(ws[kc], bf, acc);
-        }
-        const int px = wave * 32 + l31;
-        const int mx = mx0 + px;
-        const bool inside = my >= 0 && my < Ho && mx >= 0 && mx < Wo;
-        char* dst = ml + slot4(my) * MROW + px * PM;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float v[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = leaky(acc[4 * g + e] * sc1[4 * g + e] + bi1[4 * g + e], slope);
-            *(uint2*)(dst + (8 * g + 4 * h) * 2) = inside ? make_uint2(Elem<T>::pack2(v[0], v[1]), Elem<T>::pack2(v[2], v[3])) : make_uint2(0u, 0u);
-        }
+        const int px = wave * 32 + l31, mx = mx0 + px;
+        mid_tile<T>(xl + slot4(my) * XROW + px * PX + h * 16, ml + slot4(my) * MROW + px * PM, ws, sc1, bi1, slope, h,
+                    my >= 0 && my < Ho && mx >= 0 && mx < Wo);
     };
     // the 3x3 of output row oy over mid rows oy-1 .. oy+1, then its epilogue: folded BN, LeakyReLU, + x (ring row oy, fp32),
     // one rounding, 16-byte row stores
     auto cons_b = [&](int oy) {
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-            const char* rowp = ml + slot4(oy - 1 + kh) * MROW + (wave_p * 32 + l31) * PM + h * 16;
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw)
-#pragma unroll
-                for (int kc = 0; kc < 2; ++kc) {
-                    const uint4 bf = *(const uint4*)(rowp + kw * PM + kc * 32);
-                    acc = mfma16<T>(A[(kh * 3 + kw) * 2 + kc], bf, acc);
-                }
-        }
-        const char* xres = xl + slot4(oy) * XROW + eco * 2;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4 v = {acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
-            *(f32x4*)(scr + l31 * 144 + (8 * g + 4 * h) * 4) = v;
-        }
-        wave_lds_fence();
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int px = wave_p * 32 + erow0 + 16 * k;              // output pixel of the strip
-            float v[8];
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const f32x4 t4 = *(const f32x4*)(scr + (erow0 + 16 * k) * 144 + (ecol * 8 + 4 * q) * 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[4 * q + e] = t4[e];
-            }
-            const uint4 rv = *(const uint4*)(xres + (px + 1) * PX);   // ring pixel px + 1 = map column ox0 + px
-            const uint32_t w[4] = {rv.x, rv.y, rv.z, rv.w};
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = leaky(v[e] * sc2[e] + bi2[e], slope);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                v[2 * q] += Elem<T>::lo(w[q]);
-                v[2 * q + 1] += Elem<T>::hi(w[q]);
-            }
-            const int ox = ox0 + px;
-            if (ox < ox_end)
-                *(uint4*)(a.y + ((((long long)n * Ho + oy) * Wo + ox) * C + eco) * 2) =
-                    make_uint4(Elem<T>::pack2(v[0], v[1]), Elem<T>::pack2(v[2], v[3]), Elem<T>::pack2(v[4], v[5]), Elem<T>::pack2(v[6], v[7]));
-        }
+        f32x16 acc[1];
+        conv3x3_rows<T, 2, 1, PM>(acc, A, [&](int kh) { return ml + slot4(oy - 1 + kh) * MROW + (wave_p * 32 + l31) * PM + h * 16; },
+                                  TapS1<PM>{});
+        res_epilogue<T, C, PX>(scr, acc[0], lane, sc2, bi2, slope, xl + slot4(oy) * XROW + eco * 2,
+                               a.y + ((((long long)n * Ho + oy) * Wo + ox0) * C + eco) * 2, wave_p * 32, ox_end - ox0);
         wave_lds_fence();
     };
 
@@ -360,19 +198,19 @@ __global__ __launch_bounds__(512) void stem_res_kernel(SRArgs a) {
         float c[4][3];
         bool ok[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) load_img(iyb, r, c[r], ok[r]);
+        for (int r = 0; r < 4; ++r) load_img(sw, iyb, r, c[r], ok[r]);
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-            if (r < 3 || tid < 128) store_img(iyb, r, c[r], ok[r]);      // 7 rows: the 8th slot belongs to row iyb + 7
+            if (r < 3 || tid < 128) store_img<T>(sw, iyb, r, c[r], ok[r]);      // 7 rows: the 8th slot belongs to row iyb + 7
     }
     __syncthreads();
     if (prod) {
 #pragma unroll
-        for (int r = 0; r < 3; ++r) stem_group(2 * pr0 - 1 + r, r, wave);
+        for (int r = 0; r < 3; ++r) stem_group<T>(sw, ws, sc1, bi1, slope, lane, 2 * pr0 - 1 + r, r, wave);
     }
     __syncthreads();
     // ring rows oy0 - 1 .. oy0 + 2 (a row past oy1 is not made); the consumer's mid rows oy0 - 1 .. oy0 + 1 follow one barrier behind
-    if (prod) { load_img(2 * pr0 + 5, 0, cimg[0], okimg[0]); prod_row(P0{}, pr0); }
+    if (prod) { load_img(sw, 2 * pr0 + 5, 0, cimg[0], okimg[0]); prod_row(P0{}, pr0); }
     __syncthreads();
     if (prod) prod_row(P1{}, pr0 + 1); else mid_row(oy0 - 1);
     __syncthreads();
@@ -399,11 +237,11 @@ __global__ __launch_bounds__(512) void stem_res_kernel(SRArgs a) {
     }
 }
 
-// strips x images x row slices to one block per CU: the slice count with the least rounds x (rows per slice + prologue)
+// strips x images x row slices to one block per CU (walker_row_slices)
 static int sr_geometry(int N, int H, int W, SRGeom& g) {
     const int Ho = H / 2, Wo = W / 2;
     // full-width strips, the last one takes the rest: a row step costs the same at every width (one 64-column MFMA step)
-    g.nstrips = (Wo + SW_MAX - 1) / SW_MAX;
+    walker_strips(Wo, SW_MAX, g.nstrips, g.strip_w);
     g.strip_w = SW_MAX;
     g.bx = (long long)N * g.nstrips;
     if (g.bx > 0x7fffffffLL) return YOLO_EUNSUPPORTED;
@@ -415,15 +253,7 @@ static int sr_geometry(int N, int H, int W, SRGeom& g) {
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
         if (dev >= 0 && dev < 64) cus_of[dev] = cus;
     }
-    const long long slots = cus;                             // one block per CU (134 KB of LDS, 8 waves)
-    long long best_s = 1;
-    double best_cost = 1e30;
-    for (long long sl = 1; sl <= (Ho >= 16 ? Ho / 8 : 1); ++sl) {
-        const long long rows = (Ho + sl - 1) / sl, nsl = (Ho + rows - 1) / rows;
-        const double cost = (double)((g.bx * nsl + slots - 1) / slots) * ((double)rows + PROLOGUE_ROWS);
-        if (cost < best_cost - 1e-9) { best_cost = cost; best_s = nsl; }
-    }
-    g.rows_per_slice = (int)((Ho + best_s - 1) / best_s);
+    g.rows_per_slice = walker_row_slices(g.bx, Ho, cus, PROLOGUE_ROWS);   // one block per CU (134 KB of LDS, 8 waves)
     g.slices = (Ho + g.rows_per_slice - 1) / g.rows_per_slice;
     if (g.slices > 65535) return YOLO_EUNSUPPORTED;
     return YOLO_OK;
