@@ -132,7 +132,9 @@ typedef struct yolo_conv_desc {
                               tile variant (csrc/conv_pipe.hip), YOLO_EUNSUPPORTED if not eligible    */
     long long x_pixel_stride; /* elements between pixels in x; 0 = dense Cin.  > Cin: x is a channel slice of a wider
                               NHWC buffer (the route half of a concat buffer, car/utils.py:93); images stay
-                              H*W*x_pixel_stride apart                                        */
+                              H*W*x_pixel_stride apart.  The pitch in BYTES must stay below 2^31
+                              (YOLO_EINVAL); pinned tile variants also refuse an x of 0xffffff00 bytes or more
+                              (YOLO_EUNSUPPORTED; algo 0 runs the generic kernel then)        */
     int upsample2x;        /* 1: every output pixel is stored to the 2x2 patch (2oy..2oy+1, 2ox..2ox+1) of a
                               (N,2Ho,2Wo,*) map -- gluoncv _upsample(x, stride=2) (car/utils.py:92) fused into the
                               producing convolution; strides then refer to that map (y_batch_stride 0 =

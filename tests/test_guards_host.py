@@ -87,6 +87,54 @@ def test_moated_operand_equals_its_source(tdt):
     assert bool((flat[lead - GUARD_BYTES:lead] == 0xFF).all()) and bool((flat[lead + nbytes:lead + nbytes + GUARD_BYTES] == 0xFF).all())
 
 
+@pytest.mark.parametrize('tdt', [torch.float32, torch.bfloat16, torch.uint8])
+def test_islands_layout_and_bands(tdt):
+    """Islands: regions `step` bytes apart in a buffer that is never filled as a whole; each region reads as the poison, the strided
+    view addresses region i as [i], and a byte written in any band -- not between the bands -- is found and located."""
+    from util import Islands
+    es = torch.empty((), dtype=tdt).element_size()
+    shape, n, step = (3, 5, 8), 3, 5 * GUARD_BYTES + 4096
+    used = 3 * 5 * 8 * es
+    isl = Islands(n, used, step, 'cpu')
+    assert isl.buf.dtype == torch.uint8 and isl.buf.numel() == (n - 1) * step + used + 2 * GUARD_BYTES and isl.buf.data_ptr() % 512 == 0
+    v = isl.view(shape, tdt)
+    assert tuple(v.shape) == (n,) + shape and v.dtype == tdt and v.stride(0) * es == step and v[1].is_contiguous()
+    assert v.data_ptr() == isl.data_ptr() == isl.buf.data_ptr() + GUARD_BYTES
+    for i in range(n):
+        assert v[i].data_ptr() == isl.data_ptr() + i * step == isl.region(i).data_ptr()
+        assert bool((isl.region(i) == 0xFF).all())
+        if tdt.is_floating_point:
+            assert bool(torch.isnan(v[i]).all())
+    assert isl.intact()
+    v.zero_()                                                           # writing every region leaves the bands alone
+    assert isl.intact() and bool((isl.region(2) == 0).all())
+    isl.buf[step + 3 * GUARD_BYTES] = 0x12                              # between the bands of regions 1 and 2: nobody's
+    assert isl.intact()
+    isl.buf[step + GUARD_BYTES - 1] = 0                                 # the byte just before region 1
+    with pytest.raises(AssertionError, match=r'before region 1 .* offset -1 from the region \(1 changed\)'):
+        isl.intact()
+    isl.buf[step + GUARD_BYTES - 1] = 0xFF
+    isl.buf[2 * step + GUARD_BYTES + used] = 0                          # the byte just behind region 2, and the last one of its band
+    isl.buf[-1] = 0
+    with pytest.raises(AssertionError, match=r'behind region 2 .* offset %d from the region \(2 changed\)' % used):
+        isl.intact()
+    isl.buf[2 * step + GUARD_BYTES + used] = 0xFF
+    with pytest.raises(AssertionError, match=r'behind region 2 .* offset %d from' % (used + GUARD_BYTES - 1)):
+        isl.intact()
+    isl.buf[-1] = 0xFF
+    isl.buf[0] = 7                                                      # the first byte of the first band
+    with pytest.raises(AssertionError, match=r'before region 0 .* offset -%d from' % GUARD_BYTES):
+        isl.intact()
+
+
+def test_islands_refuses_overlapping_regions():
+    from util import Islands
+    with pytest.raises(AssertionError):
+        Islands(2, 4096, 4096 + GUARD_BYTES, 'cpu')                     # (the bands of neighbours would share bytes with a region)
+    with pytest.raises(AssertionError):
+        Islands(2, 4096, 4 * GUARD_BYTES + 8, 'cpu')                    # (steps are whole 16-byte units)
+
+
 def test_prior_contents_for_accumulating_outputs():
     prior = torch.arange(12, dtype=torch.float32).view(3, 4)
     buf, view = guarded((3, 4), torch.float32, 'cpu', prior=prior)

@@ -213,6 +213,71 @@ def test_conv_variant_eligibility_rules():
     assert n_stats == 246
 
 
+def _kernel_name(lib, case, dtype, algo, **fields):
+    """(status, kernel name) of yolo_conv_kernel_name for a conv case with further descriptor members: no launch."""
+    from yolo_amd import lib as L
+    from util import LDT
+    N, Cin, H, W, Cout, k, stride = case
+    d = L.ConvDesc()
+    d.x = d.w_packed = d.y = 4096
+    d.N, d.H, d.W, d.Cin, d.Cout, d.ksize, d.stride, d.dtype, d.slope, d.algo = N, H, W, Cin, Cout, k, stride, LDT[dtype], 0.1, algo
+    for f, v in fields.items():
+        setattr(d, f, 4096 if v is True else v)
+    buf = C.create_string_buffer(256)
+    rc = lib.yolo_conv_kernel_name(C.byref(d), buf, 256)
+    return rc, buf.value.decode()
+
+
+def test_conv_input_pixel_pitch_is_bounded_in_bytes(lib):
+    """The kernels hold the pitch of an input pixel, x_pixel_stride * sizeof(T), as an int: a pitch beyond INT_MAX BYTES is an
+    argument error (it used to be accepted up to INT_MAX ELEMENTS and wrapped from 2^30 elements of a 2-byte type, 2^29 of
+    fp32), the largest 16-byte aligned pitch below it is taken by the generic kernel, which has no limit on the extent of x."""
+    from yolo_amd import lib as L
+    case = (1, 64, 2, 2, 64, 1, 1)
+    for dtype, es in (('bf16', 2), ('f16', 2), ('bf16x3', 2), ('f32', 4)):
+        over, under = (1 << 31) // es, ((1 << 31) - 16) // es
+        assert _kernel_name(lib, case, dtype, 1, x_pixel_stride=over)[0] == L.EINVAL, dtype
+        assert _kernel_name(lib, case, dtype, 0, x_pixel_stride=over)[0] == L.EINVAL, dtype
+        assert _kernel_name(lib, case, dtype, 1, x_pixel_stride=(1 << 31) - 8)[0] == L.EINVAL, dtype       # (the old bound, in elements)
+        rc, name = _kernel_name(lib, case, dtype, 1, x_pixel_stride=under)
+        assert rc == 0 and 'conv_igemm_kernel' in name, (dtype, rc, name)
+
+
+def test_conv_32bit_offset_limits(lib):
+    """The pipelined and split-K kernels keep input offsets as 32-bit unsigned bytes with ~0 as the marker of a padding slot: an x
+    extent N*H*W*x_pixel_stride*es of 0xffffff00 is refused, one 16-byte step of the pitch below it is taken; algo 0 then falls
+    through to the generic kernel (64-bit offsets).  The fused tail reads y back the same way: N*y_batch_stride*2 bytes.  The
+    data-gradient sums (stats_mode 2) read stats_y through 64-bit addresses and have no such limit."""
+    from yolo_amd import lib as L
+    LIMIT = 0xffffff00
+    for dtype, es in (('bf16', 2), ('f32', 4)):
+        # 16 pixels x pitch: 16 * 268435440 = 0xffffff00
+        at = 268435440 // es
+        assert 16 * at * es == LIMIT
+        for case, algos in (((1, 256, 4, 4, 128, 3, 1), (4, 2)), ((1, 256, 4, 4, 128, 1, 1), (11, 19, 22, 30))):
+            for algo in algos:
+                assert _kernel_name(lib, case, dtype, algo, x_pixel_stride=at)[0] == L.EUNSUPPORTED, (case, dtype, algo)
+                rc, name = _kernel_name(lib, case, dtype, algo, x_pixel_stride=at - 16 // es)
+                assert rc == 0 and ('conv_pipe_kernel' in name or 'conv_sk_kernel' in name), (case, dtype, algo, rc, name)
+            rc, name = _kernel_name(lib, case, dtype, 0, x_pixel_stride=at)
+            assert rc == 0 and 'conv_igemm_kernel' in name, (case, dtype, rc, name)
+            rc, name = _kernel_name(lib, case, dtype, 0, x_pixel_stride=at - 16 // es)
+            assert rc == 0 and 'conv_igemm_kernel' not in name, (case, dtype, rc, name)
+    # fused tail: N = 2 images 0x7fffff80 bytes apart
+    case = (2, 128, 13, 13, 256, 3, 1)
+    tail = dict(tail_w_packed=True, tail_y=True, tail_cout=128, tail_slope=0.1)
+    at = LIMIT // 4
+    for algo in (2, 6, 0):
+        assert _kernel_name(lib, case, 'bf16', algo, y_batch_stride=at, **tail)[0] == L.EUNSUPPORTED, algo
+        rc, name = _kernel_name(lib, case, 'bf16', algo, y_batch_stride=at - 8, **tail)
+        assert rc == 0 and name.endswith(', 3>(ConvArgs)'), (algo, rc, name)
+    # data-gradient sums: at the same stride and far beyond it (6 GiB)
+    from util import conv_variant
+    for ybs in (at, 3 * (1 << 30) // 2):
+        for algo in (2, 4):
+            assert conv_variant(case, 'bf16', algo, stats_mode=2, fields=dict(y_batch_stride=ybs)) is not None, (ybs, algo)
+
+
 def test_launch_plan_round_trip_and_committed_file():
     """yolo_amd/plans.py: tuning states survive the JSON file (nested tuple keys, bools as 0 / 1), the md5 is over the contents, and
     the COMMITTED plan (profiles/plan.json, what bench.py launches by default) loads and holds choices for the three sections."""

@@ -59,6 +59,55 @@ def moated(t):
     return guarded(t.shape, t.dtype, t.device, prior=t)[1]
 
 
+class Islands:
+    """guarded() for tensors whose EXTENT is large and whose used bytes are few (an image every 1.5 GiB, a pixel every 48 MiB): `n`
+    regions of `used` bytes, `step` bytes apart, in one flat uint8 buffer that comes from torch.empty and is never filled as a whole.
+    Only each region and the GUARD_BYTES before and behind it are written -- 0xFF, the poison / sentinel of guarded() -- and exactly
+    those bands are checked by intact().  Region 0 starts at a multiple of 512 bytes of the address space."""
+
+    def __init__(self, n, used, step, dev):
+        self.n, self.used, self.step = int(n), int(used), int(step)
+        assert self.n >= 1 and self.used > 0 and self.step % 16 == 0 and (self.n == 1 or self.step >= self.used + 2 * GUARD_BYTES)
+        self.total = (self.n - 1) * self.step + self.used + 2 * GUARD_BYTES
+        raw = torch.empty(self.total + 512, dtype=torch.uint8, device=dev)
+        lead = -raw.data_ptr() % 512
+        self.buf = raw[lead:lead + self.total]
+        for i in range(self.n):
+            self.buf[i * self.step:i * self.step + self.used + 2 * GUARD_BYTES].fill_(0xFF)
+
+    def region(self, i):
+        """The `used` bytes of region i (uint8)."""
+        o = i * self.step + GUARD_BYTES
+        return self.buf[o:o + self.used]
+
+    def view(self, shape, tdt):
+        """(n,) + shape in `tdt`: region i is [i], a dense tensor of `shape`; the first stride is step bytes."""
+        shape = tuple(int(v) for v in shape)
+        es = torch.empty((), dtype=tdt).element_size()
+        assert int(np.prod(shape, dtype=np.int64)) * es == self.used and self.step % es == 0
+        strides, s = [], 1
+        for v in reversed(shape):
+            strides.append(s)
+            s *= v
+        flat = self.buf[GUARD_BYTES:].view(tdt)
+        return torch.as_strided(flat, (self.n,) + shape, (self.step // es,) + tuple(reversed(strides)))
+
+    def data_ptr(self):
+        return self.buf.data_ptr() + GUARD_BYTES
+
+    def intact(self):
+        """Every band still holds 0xFF in every byte; otherwise names the first changed byte by its region and its offset from the
+        region's first byte (negative: before it; >= used: behind it), as guards_intact() does."""
+        for side, first in (('before', 0), ('behind', GUARD_BYTES + self.used)):
+            bands = torch.as_strided(self.buf, (self.n, GUARD_BYTES), (self.step, 1), self.buf.storage_offset() + first)
+            bad = bands != 0xFF
+            if bool(bad.any()):
+                i, b = (int(v) for v in bad.nonzero()[0])
+                raise AssertionError('guard %s region %d (%d bytes every %d) was written: first changed byte at offset %d from the region '
+                                     '(%d changed)' % (side, i, self.used, self.step, first - GUARD_BYTES + b, int(bad.sum())))
+        return True
+
+
 KERNEL_SETS = ('measured', 'plan')
 
 
@@ -190,11 +239,12 @@ def ref_conv_split(x, w, scale, bias, stride, slope, residual=None, rdt=torch.bf
     return y.numpy()
 
 
-def conv_variant(case, dtype, algo, stats_mode=0, residual=None):
+def conv_variant(case, dtype, algo, stats_mode=0, residual=None, fields=None):
     """Which kernel instantiation `algo` runs for a conv case (N, Cin, H, W, Cout, k, stride[, residual]) -- None when the library
     refuses the pair.  A host-side query (yolo_conv_kernel_name / yolo_conv_stats_rows: no launch, no GPU), so the GPU tests
     are parametrised over the ELIGIBLE (shape, variant) pairs only and a skip means something again; the refusal rules
-    themselves are asserted by tests/test_host.py::test_conv_variant_eligibility_rules."""
+    themselves are asserted by tests/test_host.py::test_conv_variant_eligibility_rules.  `fields`: further yolo_conv_desc members
+    (the strides, upsample2x, out_f32, the tail: {'y_batch_stride': ..}) -- a pointer member set to True gets a dummy address."""
     lib = L.load()
     N, Cin, H, W, Cout, k, stride = case[:7]
     d = L.ConvDesc()
@@ -203,6 +253,8 @@ def conv_variant(case, dtype, algo, stats_mode=0, residual=None):
         d.residual = 4096
     d.N, d.H, d.W, d.Cin, d.Cout, d.ksize, d.stride = N, H, W, Cin, Cout, k, stride
     d.dtype, d.slope, d.algo = LDT[dtype], (1.0 if stats_mode else 0.1), algo
+    for k_, v in (fields or {}).items():
+        setattr(d, k_, 4096 if v is True else v)
     if stats_mode:
         d.stats, d.stats_mode = 4096, stats_mode
         if stats_mode == 2:

@@ -472,7 +472,8 @@ static int conv_dispatch(const yolo_conv_desc* d, void* stream, const NameOut* n
     a.d2s = 0;
     a.halo_strict = 0;
     a.up2 = d->upsample2x ? 1 : 0;
-    if (d->x_pixel_stride < 0 || (d->x_pixel_stride && d->x_pixel_stride < (long long)cin_p * planes) || d->x_pixel_stride > 0x7fffffffLL) return YOLO_EINVAL;
+    // (the bound is on BYTES: the kernels hold the pixel pitch x_ps * sizeof(T) as an int)
+    if (d->x_pixel_stride < 0 || (d->x_pixel_stride && d->x_pixel_stride < (long long)cin_p * planes) || d->x_pixel_stride > 0x7fffffffLL / es) return YOLO_EINVAL;
     a.x_ps = d->x_pixel_stride ? (int)d->x_pixel_stride : cin_p * planes;
     a.x3_n = 0; a.x3_adj1 = 0; a.x3_adj2 = 0; a.y_lo = 0; a.r_lo = 0;
     if (split) {
