@@ -748,8 +748,22 @@ int yolo_bn_train_bwd_partials(const float* partials, int rows, int cout_pad, co
  * dy (N,Ho,Wo,[dy_pixel_stride]) x (N,H,W,Cin), NHWC `dtype`.  The caller zero-fills dw once per step.
  * YOLO_F32: MFMA 32x32x2 f32.  YOLO_BF16: MFMA 32x32x16 bf16 fed by transposing LDS reads
  * (ds_read_b64_tr_b16), fp32 accumulation; needs `workspace` of yolo_conv_wgrad_workspace_bytes(), ZERO-FILLED by
- * the caller before its first use; every call leaves it zeroed again.  bf16: x must be smaller than 4 GiB (32-bit
- * buffer offsets; YOLO_EUNSUPPORTED otherwise). */
+ * the caller before its first use; every call leaves it zeroed again.
+ * Extents (NOTES.md, "Offsets past 2^31 and 2^32 bytes: the training step").  YOLO_F32: 64-bit offsets, any extent of x and
+ * dy.  YOLO_BF16, by the path yolo_conv_wgrad takes:
+ *   - 1x1 with Cin and Cout multiples of 128 (the LDS-DMA GEMM): x and dy each below 0xfffffe00 bytes; from there on the
+ *     per-tap kernel;
+ *   - 3x3 stride 1 with Cin and Cout multiples of 64 (the row walk): x and dy each below 0xffffff00 bytes; from there on the
+ *     next path that takes the shape;
+ *   - 3x3 with Cin <= 64, the stride-2 layer with Cin == 64 apart (the column-strip kernel), and 3x3 stride 1 with W <= 40 at
+ *     a width the row-group kernel has a variant for: 64-bit bases, ANY extent of x and dy, 4 GiB and more included;
+ *   - everything else (the per-tap kernel): x below 0xffffff00 bytes (32-bit buffer offsets), YOLO_EUNSUPPORTED from there
+ *     on; dy any extent.
+ * So an x of 4 GiB or more is computed by the strip and row-group paths and refused with YOLO_EUNSUPPORTED, nothing written,
+ * by the last.  N*H*W and N*Ho*Wo stay below 2^31 - 1.  dy_pixel_stride (bf16: % 8 == 0, not negative): the strip, row-group
+ * and per-tap kernels reach 32 (stride 1: Wo + 32), 112 and 64 pixels of dy through 32-bit lane offsets; at a pitch at which
+ * that span passes 2^31 bytes the first two hand the call on to the per-tap kernel, and the per-tap kernel answers
+ * YOLO_EUNSUPPORTED (pitches of tens of MB per pixel: no caller has one). */
 long long yolo_conv_wgrad_workspace_bytes(int Cin, int Cout, int ksize, int dtype);
 int yolo_conv_wgrad(const void* dy, const void* x, float* dw_oihw, int N, int H, int W, int Cin, int Cout,
                     int ksize, int stride, long long dy_pixel_stride, int dtype, void* workspace,
@@ -770,7 +784,8 @@ int yolo_conv_wgrad_algo(const void* dy, const void* x, float* dw_oihw, int N, i
  * slice of wider rows.  k in {1, 3}, stride in {1, 2}.  workspace: yolo_conv_wgrad_split_workspace_bytes(), ZERO-FILLED by the
  * caller before its first use; every call leaves it zeroed again.  algo: 0 = the library's choice, 1 = 64 x 64 tiles,
  * 2 = 128 x 128 tiles.  The kernel's offsets into x are 32-bit: a batch whose x reaches 4 GiB (both planes count) runs as several
- * launches over slices of whole images; YOLO_EUNSUPPORTED only when ONE image's x does. */
+ * launches over slices of whole images; YOLO_EUNSUPPORTED only when ONE image's x does.  dy: any extent (a 64-bit base per
+ * 32-pixel chunk); 33 pixels of dy_pixel_stride stay below 2^31 bytes (YOLO_EUNSUPPORTED otherwise). */
 long long yolo_conv_wgrad_split_workspace_bytes(int Cin, int Cout, int ksize, int dtype);
 int yolo_conv_wgrad_split(const void* dy, const void* x, float* dw_oihw, int N, int H, int W, int Cin, int Cout,
                           int ksize, int stride, long long dy_pixel_stride, long long dy_lo_offset, int dtype,

@@ -7,7 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import graph as og, train as ot
-from util import split_planes
+from util import split_planes, ab_counts, ab_tensor
 from yolo_amd import lib as L
 
 pytestmark = pytest.mark.gpu
@@ -195,15 +195,20 @@ def test_split_wgrad_padded_rows_and_refusals(lib, cuda):
 
 
 def test_split_wgrad_batch_past_4gib(lib, cuda):
-    """A batch whose split x reaches 4 GiB (the kernel's offsets are 32-bit) runs as launches over slices of whole images: 200
-    copies of one 416^2 8-channel image (4.4 GB of x, likewise of dy) give 200 times the one image's gradient."""
-    N, Cin, H, W, Cout = 200, 8, 416, 416, 32
+    """A batch whose split x reaches 4 GiB (the kernel's offsets are 32-bit) runs as launches over slices of whole images.  The
+    batch is two different 416^2 8-channel images (tests/util.py ab_counts): the 193 copies that lie wholly below 2^32 bytes are A,
+    the 65 from the one that touches the line onward are B (5.7 GB of x, likewise of dy), and an image's 22 MB do not divide 2^32 --
+    so a slice that started at the wrong image, or an offset that wrapped, would change the sum: dw / N is
+    (nA dw(A) + nB dw(B)) / N."""
+    Cin, H, W, Cout = 8, 416, 416, 32
     rng = np.random.default_rng(21)
-    x1 = _to_split(rng.standard_normal((1, H, W, Cin)).astype(np.float32), cuda)
-    d1 = _to_split(rng.standard_normal((1, H, W, Cout)).astype(np.float32), cuda)
-    ref = _wgrad_ref(_val(x1, Cin).numpy(), _val(d1, Cout).numpy(), 3, 1)
-    assert N * x1[0].numel() * 2 >= 4 << 30
-    xs, ds = x1.expand(N, -1, -1, -1, -1).contiguous(), d1.expand(N, -1, -1, -1, -1).contiguous()
+    x2 = _to_split(rng.standard_normal((2, H, W, Cin)).astype(np.float32), cuda)
+    d2 = _to_split(rng.standard_normal((2, H, W, Cout)).astype(np.float32), cuda)
+    nA, nB = ab_counts(32, x2[0].numel() * 2)
+    N = nA + nB
+    ref = sum(n * _wgrad_ref(_val(x2[i:i + 1], Cin).numpy(), _val(d2[i:i + 1], Cout).numpy(), 3, 1) for i, n in ((0, nA), (1, nB))) / N
+    assert nA * x2[0].numel() * 2 < 1 << 32 < (nA + 1) * x2[0].numel() * 2 and nB * 4 >= N
+    xs, ds = ab_tensor(x2[0], x2[1], nA, nB, cuda)[1], ab_tensor(d2[0], d2[1], nA, nB, cuda)[1]
     ws = torch.zeros(lib.yolo_conv_wgrad_split_workspace_bytes(Cin, Cout, 3, DT), dtype=torch.uint8, device=cuda)
     for algo in (0, 2):
         dw = torch.zeros((Cout, Cin, 3, 3), dtype=torch.float32, device=cuda)

@@ -108,6 +108,50 @@ class Islands:
         return True
 
 
+# ---- really filled tensors across an offset line (tests/test_gpu_large_offsets_train.py): kernels that reduce over, or rewrite, the
+# whole tensor cannot use Islands.  The tensor is N copies of two small images: A below the line, B from the image that touches it
+def ab_counts(line, image_bytes):
+    """-> (nA, nB) for a tensor of images of `image_bytes` across the 2^line-byte line: the nA images that lie wholly below the
+    line are A, image nA touches it and is the first of nB images B, nB >= (nA + nB) / 4.  image_bytes must not divide 2^line: an
+    offset that wraps by 2^31 or 2^32 then lands on the wrong image at the wrong phase."""
+    assert (1 << line) % image_bytes, 'the image size divides the line'
+    nA = (1 << line) // image_bytes
+    return nA, max(1, -(-nA // 3))
+
+
+def ab_fill(t, a, b, nA):
+    """t (N, ...) on the device <- image a in [0, nA), image b from nA on (a, b: one image each, on the device or the host)."""
+    t[:nA].copy_(a.to(t.device), non_blocking=True)
+    t[nA:].copy_(b.to(t.device), non_blocking=True)
+    return t
+
+
+def ab_tensor(a, b, nA, nB, dev, guard=False):
+    """-> (buf or None, t): the (nA + nB, ...) tensor of ab_fill, built on the device; guard: between guard bands (guarded())."""
+    shape = (nA + nB,) + tuple(a.shape)
+    buf, t = guarded(shape, a.dtype, dev) if guard else (None, torch.empty(shape, dtype=a.dtype, device=dev))
+    return buf, ab_fill(t, a, b, nA)
+
+
+def bits_of(t):
+    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+def ab_images_equal(t, nA, what):
+    """Every image of t[:nA] equals t[0] and every image of t[nA:] equals t[nA], bit for bit, compared on the device in pieces of
+    256 MiB."""
+    N = t.shape[0]
+    flat = bits_of(t.view(N, -1))
+    per = max(1, (256 << 20) // (flat.shape[1] * flat.element_size()))
+    for first, lo, hi in ((0, 0, nA), (nA, nA, N)):
+        for i in range(lo, hi, per):
+            same = (flat[i:min(i + per, hi)] == flat[first:first + 1]).all(dim=1)
+            if not bool(same.all()):
+                n = i + int((~same).nonzero()[0])
+                raise AssertionError('%s: image %d of %d (byte offset %d) differs from image %d' %
+                                     (what, n, N, n * flat.shape[1] * flat.element_size(), first))
+
+
 KERNEL_SETS = ('measured', 'plan')
 
 

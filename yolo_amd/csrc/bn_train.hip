@@ -18,6 +18,8 @@
 // 13x13 maps ran on 64 blocks at 0.65 TB/s)
 constexpr int BN_CG = 256;
 
+// (tests/test_gpu_large_offsets_train.py `_bn_chain` restates these constants to bound the fp32 terms a thread of the reduction adds:
+//  change them there too)
 static void bn_partition(long long npix, int C, int elem, bool reduces, int* ppb, unsigned* nb) {
     const int cb = (reduces && C > BN_CG) ? BN_CG : C;          // channels per block
     // (measured over the training step: 64 KB per block beats 32 / 128 KB by 0.3 / 0.4 ms; twice / four times the atomics
@@ -104,8 +106,25 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const T* __restrict__ y,
                     load8s<T>(yp + (p + (long long)u * lanes) * PS, LO, v[u]);
                     if (MODE == 1) load8s<T>(dp + (p + (long long)u * lanes) * PS, LO, d[u]);
                 }
+                if (MODE == 0 && IsSplit<T>::value) {
+                    // Split values carry 16 significant bits, so next to a running sum of a few hundred EVERY fp32 addition is a
+                    // tie or exact, and ties to an even sum all round the same way: over the hundreds of terms a thread adds on
+                    // a tensor of 10^7 pixels the mean lost 5 bits (9e-7 at values of std 2 -- tests/
+                    // test_gpu_large_offsets_train.py).  The U values of a step are summed on their own first: small sums, exact
+                    // for such values, and an eighth of the additions into the running one.
+                    float ts[8], tq[8];
 #pragma unroll
-                for (int u = 0; u < U; ++u) accum(v[u], MODE == 1 ? d[u] : v[u]);
+                    for (int e = 0; e < 8; ++e) ts[e] = tq[e] = 0.f;
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) { const float dv = v[u][e] - mu[e]; ts[e] += dv; tq[e] += dv * dv; }
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) { s[e] += ts[e]; q[e] += tq[e]; }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < U; ++u) accum(v[u], MODE == 1 ? d[u] : v[u]);
+                }
             }
             for (; p < p1; p += lanes) {
                 float v[8], d[8];

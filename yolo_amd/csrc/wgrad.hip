@@ -483,7 +483,7 @@ __global__ __launch_bounds__(64) void wgrad_strip_kernel(const uint16_t* __restr
         const int u = lane + j * 64;
         const int part = u % (CO_F * 4), px = (u / (CO_F * 4)) % TW, t = u / (CO_F * 4 * TW);
         d_row[j] = (ox0 + px < Wo && co0 + part * 8 < Cout) ? t : -1;
-        d_off[j] = (int)(((long long)t * Wo + px) * dy_ps + part * 8) * 2;
+        d_off[j] = (int)((((long long)t * Wo + px) * dy_ps + part * 8) * 2);       // (the host bounds TH rows of dy below 2^31 bytes)
     }
     typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
     auto load_x = [&](auto set_c, int iy0) {
@@ -852,6 +852,10 @@ __global__ void wgrad_finish_kernel(float* __restrict__ dwt, float* __restrict__
     dwt[j] = 0.f;                                    // leave the workspace zeroed for the next call (no memset launch)
 }
 
+// The dy side of the bf16 and split kernels: a 64-bit base per chunk / strip step / row group, and `int` lane offsets behind it
+// that span `pixels` pixels of the caller's pitch (d_off, d_goff).  They must stay below 2^31 bytes.
+static bool dy_lanes_fit(long long pixels, long long ps) { return ps <= (0x7fffffffLL - 4096) / (2 * pixels); }
+
 extern "C" long long yolo_conv_wgrad_workspace_bytes(int Cin, int Cout, int ksize, int dtype) {
     if (Cin <= 0 || Cout <= 0 || (ksize != 1 && ksize != 3) || (dtype != YOLO_BF16 && dtype != YOLO_F32)) return YOLO_EINVAL;
     if (dtype != YOLO_BF16) return 0;
@@ -879,6 +883,7 @@ extern "C" int yolo_conv_wgrad_algo(const void* dy, const void* x, float* dw_oih
         return yolo_conv_wgrad_f32((const float*)dy, (const float*)x, dw_oihw, N, H, W, Cin, Cout, ksize, stride,
                                    dy_pixel_stride, stream);
     if (dtype != YOLO_BF16) return YOLO_EINVAL;
+    if (dy_pixel_stride < 0) return YOLO_EINVAL;
     const long long ps = dy_pixel_stride ? dy_pixel_stride : Cout;
     if (!workspace || (Cin % 8) || (ps % 8)) return YOLO_EUNSUPPORTED;
     if ((long long)N * H * W >= 0x7fffffffLL) return YOLO_EUNSUPPORTED;
@@ -903,7 +908,11 @@ extern "C" int yolo_conv_wgrad_algo(const void* dy, const void* x, float* dw_oih
         return YOLO_EUNSUPPORTED;
     }
     // (the 64 -> 128 stride-2 layer: the per-tap kernel measures 388 us against the strip kernel's 503 at 208^2 bs 64)
-    if (ksize == 3 && Cin <= 64 && !(stride == 2 && Cin == 64)) {
+    // (x: 64-bit bases per step, so any extent; dy: the lane offsets span TH rows of a 32-pixel strip -- a pitch too wide for that
+    //  goes on to the per-tap kernel, and so does a row so wide that the `int x_off` of the two staged rows would pass 2^31 bytes:
+    //  millions of columns)
+    if (ksize == 3 && Cin <= 64 && !(stride == 2 && Cin == 64) && dy_lanes_fit((stride == 2 ? 0LL : Wo) + 32, ps) &&
+        (2LL * W + 128) * Cin * 2 < 0x7fffffffLL) {
         const uint16_t* d16 = (const uint16_t*)dy;
         const uint16_t* x16 = (const uint16_t*)x;
         float* ws = (float*)workspace;
@@ -917,7 +926,8 @@ extern "C" int yolo_conv_wgrad_algo(const void* dy, const void* x, float* dw_oih
     }
     // row-group kernel: wins on the narrow deep maps (26x26: 210 -> 163 us, 13x13: 211 -> 175 us at batch 64); on wider
     // maps its atomic epilogue (one 64x64x9 tile per block) costs more than the saved L2 traffic
-    if (ksize == 3 && stride == 1 && W <= 40) {
+    // (x: a 64-bit base per row group, so any extent; dy: the lane offsets span a group of at most 7 * 16 pixels -- as above)
+    if (ksize == 3 && stride == 1 && W <= 40 && dy_lanes_fit(112, ps)) {
         if (wgrad_rows_dispatch((const uint16_t*)dy, (const uint16_t*)x, (float*)workspace, N, H, W, Cin, Cout, ps, st)) {
             YOLO_LAUNCH(wgrad_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
                         (float*)workspace, dw_oihw, Cout, Cin, taps, total);
@@ -932,6 +942,7 @@ extern "C" int yolo_conv_wgrad_algo(const void* dy, const void* x, float* dw_oih
         // (256x128 / 128x256 / 256x256 tiles were measured 10-40 % slower: one wave per SIMD)
         if ((long long)N * H * W * Cin * 2 >= 0xffffff00LL || (long long)N * Ho * Wo >= 0x7fffffffLL)
             return YOLO_EUNSUPPORTED;                        // (32-bit buffer offsets into x)
+        if (!dy_lanes_fit(WG_KC, ps)) return YOLO_EUNSUPPORTED;  // (dy: the lane offsets span one K-chunk)
         wgrad_bf16_launch<2, 2>(d16, x16, ws, N, H, W, Cin, Ho, Wo, Cout, ksize, stride, ps, st);
     }
     YOLO_LAUNCH(wgrad_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (float*)workspace,
@@ -969,6 +980,7 @@ extern "C" int yolo_conv_wgrad_split(const void* dy, const void* x, float* dw_oi
     if (per * img_bytes >= 0xffffff00LL) per = (0xffffff00LL - 1) / img_bytes;
     if (per * Ho * Wo >= 0x7fffffffLL) per = (0x7fffffffLL - 1) / ((long long)Ho * Wo);
     if (per < 1 || lo * 2 >= 0x7fff0000LL) return YOLO_EUNSUPPORTED;            // (one image alone past the limit)
+    if (!dy_lanes_fit(SWG_KC + 1, ps)) return YOLO_EUNSUPPORTED;                // (dy: a K-chunk of pixels and the lo plane behind the last)
     hipStream_t st = (hipStream_t)stream;
     (void)hipGetLastError();
     const int taps = ksize * ksize;
