@@ -844,6 +844,53 @@ int yolo_adam_step(float* w, const float* grad, float* m, float* v, long long n,
 int yolo_adam_step_dev(float* w, const float* grad, float* m, float* v, long long n, int t, float lr,
                        float beta1, float beta2, float eps, const float* global_batch_dev, void* stream);
 
+/* ---- DenseNet bodies, inference (csrc/dense.hip) ------------------------------------------------------------------------------
+ * gluoncv's DenseNet as the reference's OCRDenseNet (OCR/OCR.py:34-74), LPDenseNet (licence_plate/LP_detection.py:59-97) and
+ * CarDenseNet (car/utils.py:48-61) build it: stem, dense blocks, transitions, a final BN + ReLU.  yolo_amd/dense.py states the
+ * network; YOLO_BF16 and YOLO_F32 only (YOLO_EUNSUPPORTED for the other valid dtypes).
+ * A block's feature map is ONE buffer (N,H,W) pixels x Cs elements, Cs = round_up(the block's final channel count, 32); its layers
+ * work in place: layer k reads channels [0, Cin) and writes [Cin, Cin + G).  Channels nobody has written yet may hold anything.
+ * Folded BN vectors (scale, bias) are what yolo_fold_bn writes: yolo_padded_channels(C) floats, 16-byte aligned -- the kernels read
+ * them in whole 32-channel chunks.
+ * DENSE OPERAND IMAGE of a matrix A (M, K), the weight layout of this unit: [ceil(M/16)][ceil(K/32)][64][8] elements of `dtype`,
+ * element j of lane l of tile (mt, kc) = A[16 mt + (l & 15)][32 kc + 8 (l >> 4) + j], zero where that is outside A -- the A
+ * fragment of v_mfma_f32_16x16x32_bf16 as 64 contiguous 16-byte vectors.  yolo_dense_operand_bytes(M, K, dtype) is its size; it is
+ * written on the host when the parameters are prepared (yolo_amd/dense.py pack_operand).  A conv1x1 (Cout, Cin) is the matrix itself;
+ * a conv3x3 (G, Cm, 3, 3) is the matrix (G, 9 * round_up(Cm, 32)) with column (3 ky + kx) * round_up(Cm, 32) + j = W[g][j][ky][kx].
+ * Every entry validates before it launches: YOLO_EINVAL for a NULL pointer, a non-positive size or an unknown dtype, YOLO_EUNSUPPORTED
+ * for a shape outside the stated limits and for a buffer of 2^31 bytes or more. */
+long long yolo_dense_operand_bytes(int M, int K, int dtype);
+/* One dense layer as one launch: a = max(0, x s1 + t1) over [0, Cin); m = W1 a (Cm channels); b = max(0, m s2 + t2) inside the image
+ * and EXACTLY 0 outside (the 3x3 pads b, not m); y = conv3x3(W2, b) (G channels, raw: no BN, no activation) stored to channels
+ * [Cin, Cin + G) of the same pixel.  Operands a, b and the weights are rounded once to `dtype`, sums are fp32 (bf16: v_mfma_f32_16x16x32_bf16,
+ * f32: v_mfma_f32_16x16x4_f32).  Channels >= Cin of the last K-chunk are masked by a select; no byte outside [Cin, Cin + G) of a pixel is
+ * written.  w1_image: operand image of (Cm, Cin); w2_image: of the (G, Cm, 3, 3) weights as above.
+ * Supported: G % 4 == 0, G <= 32, Cm % 16 == 0, Cm <= 128, Cin >= 8, Cin + G <= Cs, Cs % 32 == 0, any H, W >= 1. */
+int yolo_dense_layer_fwd(void* buf, const void* w1_image, const float* scale1, const float* bias1, const void* w2_image,
+                         const float* scale2, const float* bias2, int N, int H, int W, int Cs, int Cin, int Cm, int G, int dtype,
+                         void* stream);
+/* Stem: Conv 7x7 s2 p3 without bias (w_oihw (F0,3,7,7) float32, unpacked) over the (N,3,H,W) float32 NCHW image + folded BN + ReLU +
+ * MaxPool 3x3 s2 p1 -> channels [0, F0) of block 1's buffer (N,Hp,Wp,Cs), Hc = (H-1)/2+1, Hp = (Hc-1)/2+1.  A direct fp32
+ * convolution on the vector pipe (K = 147), one rounding at the store.  F0 % 8 == 0, F0 <= 64, Cs % 32 == 0. */
+int yolo_dense_stem_fwd(const float* x_nchw, const float* w_oihw, const float* scale, const float* bias, void* y, int N, int H, int W,
+                        int F0, int Cs, int dtype, void* stream);
+/* Transition: BN + ReLU + Conv 1x1 without bias C -> C/2 + AvgPool 2x2 s2, block buffer x (N,H,W,Cs_in) -> channels [0, C/2) of the
+ * next block's buffer y (N,H/2,W/2,Cs_out); an odd last row / column is dropped.  Computed as pool-then-convolve (linear, a quarter of
+ * the work): p = ((a00 + a01) + (a10 + a11)) * 0.25 in fp32, rounded once to `dtype`.  w_image: operand image of (C/2, C).  H, W >= 2. */
+int yolo_dense_transition_fwd(const void* x, const void* w_image, const float* scale, const float* bias, void* y, int N, int H, int W,
+                              int C, int Cs_in, int Cs_out, int dtype, void* stream);
+/* The BN + ReLU after the last block, block buffer x (N,H,W,Cs) -> a dense tensor of Cp >= C channels per pixel, channels C..Cp-1 zero:
+ * columns == 0: y (N,H,W,Cp), what a 3x3 yolo_conv_fwd reads (the LPD head); columns != 0: y (N,1,W,H*Cp), y[n][0][w][h*Cp + c] -- a
+ * (H,1) convolution without padding (the OCR head, OCR/OCR.py:63) is then a 1x1 yolo_conv_fwd with Cin = H*Cp. */
+int yolo_dense_bn_relu(const void* x, const float* scale, const float* bias, void* y, int N, int H, int W, int C, int Cs, int Cp,
+                       int columns, int dtype, void* stream);
+/* OCR.predict / valid's reading rule (OCR/OCR.py:180-201) on the device (csrc/ocr.hip): logits (N,Wp,1+ncls) float32 ->
+ * score (N,Wp) = 1 / (1 + expf(-logit 0)); column i is a PEAK iff s[i] > thr && s[i] > s[i+1] && s[i] > s[i-1] with s[-1] = s[Wp] = 0;
+ * codes (N,Wp) = at a peak the first maximum of the ncls class logits (np.argmax of their softmax), -1 elsewhere; count (N) = peaks.
+ * thr: 0.6 in predict, 0.2 in valid.  valid (N) bytes or NULL: a row with valid == 0 has no peaks (its scores are still written). */
+int yolo_ocr_decode(const float* logits, const unsigned char* valid, float* score, int* codes, int* count, int N, int Wp, int ncls,
+                    float thr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

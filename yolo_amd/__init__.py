@@ -29,4 +29,7 @@ def __getattr__(name):
     if name in ('fit_anchors', 'sample_sizes', 'anchor_quality', 'AnchorFit'):
         from . import anchors
         return getattr(anchors, name)
+    if name in ('DenseNet', 'OCRNet', 'LPDenseNet', 'PlateReader', 'OCR_NAMES', 'plate_format_ok'):
+        from . import dense
+        return getattr(dense, name)
     raise AttributeError(name)

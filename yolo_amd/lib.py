@@ -147,6 +147,12 @@ SIGNATURES = {
     'yolo_loss_lp_fwd_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(C.c_float), _f, _f, _vp]),
     'yolo_adam_step': (_i, [_vp, _vp, _vp, _vp, _ll, _i, _f, _f, _f, _f, _f, _vp]),
     'yolo_adam_step_dev': (_i, [_vp, _vp, _vp, _vp, _ll, _i, _f, _f, _f, _f, _vp, _vp]),
+    'yolo_dense_operand_bytes': (_ll, [_i, _i, _i]),
+    'yolo_dense_layer_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'yolo_dense_stem_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'yolo_dense_transition_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'yolo_dense_bn_relu': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'yolo_ocr_decode': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
 }
 
 _lib = None

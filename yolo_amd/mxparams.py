@@ -380,3 +380,108 @@ def to_gluon(graph, params, prefix='carnet0_', export=False):
             theirs = ('aux:' if ours.endswith(_AUX) else 'arg:') + theirs
         out[theirs] = a
     return out
+
+
+# ---- the DenseNet bodies (yolo_amd/dense.py: OCRNet, LPDenseNet) ---------------------------------------------------------------------
+# gluoncv's DenseNet builder is restated FROM RECALL (no real checkpoint of these nets exists here to pin the rules): `features` and
+# every dense layer / transition are HybridSequential(prefix=''), which open no naming scope of their own; a dense block is
+# HybridSequential(prefix='stage%d_') entered with its own name_scope().  So layer k of stage s owns
+# <net>stage{s}_batchnorm{2k,2k+1}_* and <net>stage{s}_conv{2k,2k+1}_weight, while the stem, the transitions, the final BatchNorm and
+# the head take the net scope's counters in creation order: conv0 stem, conv1.. transitions, then the head's two biased convolutions;
+# batchnorm0 stem, batchnorm1.. transitions, the final BatchNorm, the head's.  (OCRDenseNet: conv0..4, batchnorm0..4, conv3 / conv4
+# with a bias.)
+_DENSE_PREFIX = {'ocr': 'ocrdensenet0_', 'lpd': 'lpdensenet0_'}
+_DENSE_RE = re.compile(r'^(?:(?:arg|aux):)?(.*?)(stage(\d+)_)?(conv|batchnorm)(\d+)_(weight|bias|gamma|beta|running_mean|running_var|'
+                       r'moving_mean|moving_var)$')
+_BN = ('gamma', 'beta', 'running_mean', 'running_var')
+
+
+def gluon_dense_param_names(kind, F0, G, block_config, bn_size=4, prefix=None):
+    """OrderedDict `<our name>` -> gluon parameter name in collect_params() (registration) order; kind 'ocr' or 'lpd'.  F0, G and
+    bn_size do not enter the names; they are taken so that the call reads like the net's constructor."""
+    if kind not in _DENSE_PREFIX:
+        raise ValueError("kind must be 'ocr' or 'lpd'")
+    prefix = _DENSE_PREFIX[kind] if prefix is None else prefix
+    out = OrderedDict()
+    count = {'conv': 0, 'batchnorm': 0}
+
+    def conv(ours, scope, i, bias=False):
+        out[ours + '.weight'] = '%sconv%d_weight' % (scope, i)
+        if bias:
+            out[ours + '.bias'] = '%sconv%d_bias' % (scope, i)
+
+    def bn(ours, scope, i):
+        for s in _BN:
+            out['%s.%s' % (ours, s)] = '%sbatchnorm%d_%s' % (scope, i, s)
+
+    def top(kind_):
+        count[kind_] += 1
+        return count[kind_] - 1
+    conv('stem', prefix, top('conv'))
+    bn('stem', prefix, top('batchnorm'))
+    for s, n in enumerate(block_config):
+        scope = '%sstage%d_' % (prefix, s + 1)
+        for k in range(n):
+            pre = 'stage%d.layer%d.' % (s + 1, k)
+            bn(pre + 'bn1', scope, 2 * k)
+            conv(pre + 'conv1', scope, 2 * k)
+            bn(pre + 'bn2', scope, 2 * k + 1)
+            conv(pre + 'conv2', scope, 2 * k + 1)
+        if s != len(block_config) - 1:
+            bn('trans%d.bn' % (s + 1), prefix, top('batchnorm'))
+            conv('trans%d.conv' % (s + 1), prefix, top('conv'))
+    bn('final.bn', prefix, top('batchnorm'))
+    conv('head.conv1', prefix, top('conv'), bias=True)
+    bn('head.bn', prefix, top('batchnorm'))
+    conv('head.conv2', prefix, top('conv'), bias=True)
+    return out
+
+
+def _dense_kind(net):
+    return net.head[0], net.F0, net.G, net.block_config, net.bn_size
+
+
+def dense_to_gluon(net, params, prefix=None):
+    """A DenseNet's parameters under gluon names, in collect_params() order."""
+    out = OrderedDict()
+    for ours, theirs in gluon_dense_param_names(*_dense_kind(net), prefix=prefix).items():
+        v = params[ours]
+        out[theirs] = np.asarray(v.detach().cpu().numpy() if hasattr(v, 'detach') else v, np.float32)
+    return out
+
+
+def dense_from_gluon(net, loaded):
+    """Map an OrderedDict read from a gluon `.params` file onto a DenseNet's names BY STRUCTURE: the scope a name lies in (the net's
+    own or a stage's) and the RANK of its counter inside that scope -- neither the literal prefix nor the counter values matter
+    (a second net built in one process has other counters).  Every shape is checked against net.shapes."""
+    scopes = {}
+    for n, a in loaded.items():
+        m = _DENSE_RE.match(n)
+        if m is None:
+            raise ParamsFormatError('%r is not a gluon DenseNet parameter name' % n)
+        stage = int(m.group(3)) if m.group(2) else 0
+        ent = scopes.setdefault(stage, {'conv': {}, 'batchnorm': {}})[m.group(4)].setdefault(int(m.group(5)), {})
+        suffix = m.group(6).replace('moving', 'running')
+        if suffix in ent:
+            raise ParamsFormatError('parameter %r appears twice' % n)
+        ent[suffix] = np.asarray(a, np.float32)
+    want = {}
+    for ours, theirs in gluon_dense_param_names(*_dense_kind(net), prefix='').items():
+        m = _DENSE_RE.match(theirs)
+        stage = int(m.group(3)) if m.group(2) else 0
+        want.setdefault((stage, m.group(4)), {}).setdefault(int(m.group(5)), []).append((ours, m.group(6)))
+    out = {}
+    for (stage, kind), layers in want.items():
+        have = sorted(scopes.get(stage, {}).get(kind, {}).items())
+        if len(have) != len(layers):
+            raise ParamsFormatError('scope %s: the file has %d %s layers, the net %d' % ('stage%d' % stage if stage else 'net', len(have), kind, len(layers)))
+        for (_, got), (_, fields) in zip(have, sorted(layers.items())):
+            if sorted(got) != sorted(f for _, f in fields):
+                raise ParamsFormatError('%s: the file has %s, expected %s' % (fields[0][0], sorted(got), sorted(f for _, f in fields)))
+            for ours, f in fields:
+                if tuple(got[f].shape) != tuple(net.shapes[ours]):
+                    raise ParamsFormatError('%s: expected shape %s, the file has %s' % (ours, tuple(net.shapes[ours]), tuple(got[f].shape)))
+                out[ours] = got[f]
+    if set(scopes) - set(s for s, _ in want):
+        raise ParamsFormatError('the file has stages the net does not: %s' % sorted(set(scopes) - set(s for s, _ in want)))
+    return out
