@@ -891,6 +891,83 @@ int yolo_dense_bn_relu(const void* x, const float* scale, const float* bias, voi
 int yolo_ocr_decode(const float* logits, const unsigned char* valid, float* score, int* codes, int* count, int N, int Wp, int ncls,
                     float thr, void* stream);
 
+/* ---- OCR data, targets, losses and validation counts (csrc/ocr_data.hip) ---------------------------------------------------------
+ * Every entry validates before it launches: YOLO_EINVAL for a NULL pointer (where NULL is not stated to be allowed), a non-positive
+ * size or a misaligned pointer, YOLO_EUNSUPPORTED for a shape outside the stated limits.  Nothing is written on refusal.
+ *
+ * LPGenerator.render (yolo_modules/licence_plate_render/__init__.py:168-214) with the PIXELS made on the device: the OCR batch, a
+ * plate resized, sheared, rotated, blurred by a wide Gaussian, noised, colour-jittered and pasted onto a background.  The host decides
+ * (yolo_amd/render.py LPGenerator.draw_ocr_params) and hands over, per image, one row of YOLO_PLATE_ROW_WORDS words with the meaning
+ * yolo_plate_render gives them -- words 16..24 carry the AFFINE map (resize, shear, rotate and paste composed on the host; m6 = m7 = 0,
+ * m8 = 1), words 8..11 the paste rectangle (what PIL's tmp.paste covers; clipped to the canvas here whatever the row holds), words 25
+ * and 26 are unused -- and one row of YOLO_OCR_TAP_WORDS words for the blur: word 0 T (int, taps per side, limited to
+ * 0..YOLO_OCR_BLUR_TAPS here), words 1..T+1 the float32 weights w[0..T], w[0] the centre; the host normalises them to
+ * w[0] + 2 (w[1] + .. + w[T]) = 1.  T = 0: no blur, the weights are not read.  The plates are yolo_plate_compose's, unchanged.
+ * rows 8-byte, taps 4-byte, workspace 16-byte aligned, all ON THE DEVICE; bg (N,3,H,W) f32, out the same shape, dense.
+ * The arithmetic, every operation in fp32, in this order, nothing fused (this is the definition; tests/ocr_render_ref.py restates it):
+ *  S(j, i): yolo_plate_render's sample through m at the integer position (column j, row i), inside or outside the canvas.
+ *  Inside the window  Hs(j, i') = sum over k = -T..T in ascending order of w[|k|] * S(j + k, i')   (the first term starts the sum)
+ *                     P(j, i)   = sum over k = -T..T in ascending order of w[|k|] * Hs(j, i + k);  T = 0: P = S.
+ *   The taps reach S outside the window and outside the canvas.  Outside the window P = 0 and nothing is sampled.
+ *  Q(j, i) inside the window: s == 0: Q = P; otherwise yolo_plate_render's Philox / Irwin-Hall rule with the same key and counters
+ *   (j, i, h, 0) on all four channels.  Outside the window Q = 0: the reference noises the plate image before it pastes it.
+ *  yolo_ocr_plate_blur writes Q of the window's pixels to the workspace, and per 32 x 32 tile of the canvas (row-major tile index)
+ *   the sum of Q_c, c of R, G, B, over the tile's window pixels, each converted to double and added in double in a fixed order; a
+ *   tile outside the window, and every tile of a "no plate" image (yolo_plate_compose's rule), gets 0.  No atomics.  Workspace
+ *   layout (yolo_ocr_plate_workspace_bytes(N, H, W) bytes, caller-owned): N * tiles * 3 doubles, padding to a multiple of 16 bytes,
+ *   then (N,H,W,4) float32 Q of which only window pixels of images with a plate are written; no other byte is touched.
+ *  yolo_ocr_plate_render: sum_c = the image's tile sums added in index order (double);  mu_c = (float)(sum_c / (double)(H*W)) -- the
+ *   mean over the WHOLE canvas, Q = 0 outside the window;  k_c = ((D[c][0]*mu_0 + D[c][1]*mu_1) + D[c][2]*mu_2) + e_c;  per pixel
+ *   of the window   fg_c = (((A[c][0]*Q_0 + A[c][1]*Q_1) + A[c][2]*Q_2) + k_c) / 255.f;   mask = Q_3 / 255.f
+ *   out_c = min(max((bg_c * (1.f - mask)) / 255.f + fg_c * mask, 0), 1)                    (__init__.py:211; bg 0..255)
+ *   bg_unit != 0 (bg already 0..1): the division by 255 of the first term is dropped.
+ *  A pixel outside the window, and every pixel of a no-plate image: out_c = min(max(bg_c / 255.f, 0), 1) (bg_unit: of bg_c).
+ *  out may alias bg: each thread reads its pixels before it writes them.
+ * YOLO_EUNSUPPORTED: H * ceil(W / 4) beyond 2^31, more than 65535 tile rows.  16-byte bg loads and plane stores when W % 4 == 0 and
+ * bg, out are 16-byte aligned, scalar ones otherwise.
+ * Stream order: yolo_plate_compose, yolo_ocr_plate_blur, yolo_ocr_plate_render on the same rows and workspace. */
+#define YOLO_OCR_BLUR_TAPS 24
+#define YOLO_OCR_TAP_WORDS 32
+long long yolo_ocr_plate_workspace_bytes(int N, int H, int W);
+int yolo_ocr_plate_blur(const unsigned char* plates, const void* rows, const void* taps, void* workspace, int N, int H, int W,
+                        void* stream);
+int yolo_ocr_plate_render(const float* bg, const void* rows, const void* workspace, float* out, int N, int H, int W, int bg_unit,
+                          void* stream);
+/* loss_mask (OCR/OCR.py:77-100): labels (B,nobj,3) f32 [class, left, right] as fractions of the width, class < 0 (or NaN): no object;
+ * order (B,nobj) int32 or NULL: the host's draw of nd.random.shuffle -- the labels of an image are visited as order[b][0], order[b][1],
+ * ... (an entry outside 0..nobj-1 is passed over), NULL: in the given order.  score_y (B,Wp) f32, 0 where no label covers; class_y
+ * (B,Wp) int32, -1 where no label covers.  For each label in that order, in fp32:
+ *   left = round-half-away(L1 * Wp), right = round-half-away(L2 * Wp)        (limited to +-2^30)
+ *   for columns i in [max(left, 0), min(right, Wp)):  score_y = 1 - |(i + 0.5) / Wp - (L1 + L2) / 2| / (L2 - L1),  class_y = (int)class
+ * and a later label overwrites an earlier one: one thread per (image, column) keeps the last label that covers it.  Columns outside
+ * [0, Wp) are DROPPED (the reference's container wraps a negative index to the far end and raises on one >= Wp: accidents).
+ * YOLO_EUNSUPPORTED: B * Wp or B * nobj * 3 of 2^31 or more. */
+int yolo_ocr_targets(const float* labels, const int* order, float* score_y, int* class_y, int B, int nobj, int Wp, void* stream);
+/* The two losses of train_the (OCR/OCR.py:113-114, 264-265) and their gradient at the logits: logits (B,Wp,1+ncls) f32 as OCRNet.logits
+ * returns them, z = column i's score logit, c_i its ncls class logits, y_i = score_y, k_i = min(max(class_y_i, 0), ncls - 1) (pick's
+ * clip mode); losses (2,B) f32:
+ *   losses[0][b] = score_w * mean_i( max(z, 0) - z * y + log1p(exp(-|z|)) )             LogisticLoss(label_format='binary')
+ *   losses[1][b] = class_w * mean_i( y_i * (logsumexp(c_i) - c_i[k_i]) )                SoftmaxCrossEntropyLoss, sample weight score_y
+ * (the reference: score_w = 0.1, class_w = 1.0).  logsumexp(c) = max c + log(sum exp(c - max c)): finite for logits of +-100.  Per
+ * column the class terms are summed over a 64-lane butterfly, the columns of an image as four interleaved partial sums (column i in
+ * sum i % 4, in column order) added in index order.  dlogits: the same shape as logits or NULL; the gradient of sum(losses), NOT
+ * divided by the batch (yolo_loss_fwd_bwd's convention): score_w / Wp * (sigmoid(z) - y) and class_w / Wp * y * (softmax(c) - onehot(k)).
+ * YOLO_EUNSUPPORTED: logits of 2^31 bytes or more. */
+int yolo_ocr_loss_fwd_bwd(const float* logits, const float* score_y, const int* class_y, float* dlogits, float* losses, int B, int Wp,
+                          int ncls, float score_w, float class_w, void* stream);
+/* The counts of a validation step (OCR/OCR.py:301-343 reads the peaks and prints the text; this compares it with the labels): codes
+ * (B,Wp) and count (B) as yolo_ocr_decode wrote them, labels (B,nobj,3), class_y (B,Wp) from yolo_ocr_targets, logits (B,Wp,1+ncls);
+ * counts (B, YOLO_OCR_SCORE_WORDS) int32 per image:
+ *   0 truth length: the labels with class >= 0 whose centre (L1 + L2) / 2 lies in [0, 1), read left to right (by centre; ties in label order)
+ *   1 predicted length: the first count[b] non-negative codes in column order      2 the Levenshtein distance between the two texts
+ *   3 exact match (0 / 1)      4 labelled columns (class_y >= 0)      5 those whose first maximum of the class logits equals class_y
+ * One thread per image.  YOLO_EUNSUPPORTED: nobj > YOLO_OCR_SCORE_MAX_NOBJ, Wp > YOLO_OCR_SCORE_MAX_WP, logits of 2^31 bytes or more. */
+#define YOLO_OCR_SCORE_WORDS 6
+#define YOLO_OCR_SCORE_MAX_NOBJ 16
+#define YOLO_OCR_SCORE_MAX_WP 64
+int yolo_ocr_score(const int* codes, const int* count, const float* labels, const int* class_y, const float* logits, int* counts, int B,
+                   int nobj, int Wp, int ncls, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

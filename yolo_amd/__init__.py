@@ -32,4 +32,7 @@ def __getattr__(name):
     if name in ('DenseNet', 'OCRNet', 'LPDenseNet', 'PlateReader', 'OCR_NAMES', 'plate_format_ok'):
         from . import dense
         return getattr(dense, name)
+    if name in ('OCRValidator', 'ocr_targets', 'ocr_loss', 'ocr_score'):
+        from . import ocr
+        return getattr(ocr, name)
     raise AttributeError(name)

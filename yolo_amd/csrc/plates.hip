@@ -6,39 +6,17 @@
 //   plate_render_kernel   sample through the projective map, blur, noise, colour, blend over the 0..1 background, clip
 // Compiled with -ffp-contract=off: the arithmetic is the op-by-op fp32 definition of include/yolo_amd.h (yolo_plate_render), so
 // tests/plate_ref.py reproduces it bit for bit (the mean to one float32 ulp: the order of its double sum differs).  The noise is
-// integer work (Philox4x32-10, byte sums), so it is exact as well.  The tap and the blur are render.hip's (render_sample.h); one
-// thread makes 4 adjacent columns of the three planes.  The row of an image is read at a block-uniform address.
-#include "common.h"
-#include "render_sample.h"
+// integer work (Philox4x32-10, byte sums), so it is exact as well.  The tap and the blur are render.hip's (render_sample.h); the row,
+// the sample through its map and the noise are shared with the OCR batch's renderer (plate_row.h, ocr_data.hip).  One thread makes
+// 4 adjacent columns of the three planes.  The row of an image is read at a block-uniform address.
+#include "plate_row.h"
 
 constexpr int PLATE_THREADS = 256;
 constexpr int PLATE_STAT_BLOCKS = 16;                     // partial sums per image (the workspace holds 3 doubles for each)
-constexpr int PLATE_H = 160, PLATE_W = 380;               // the plate image (draw_LP)
-constexpr int GLYPH_H = 90, GLYPH_W = 45, GLYPH_TOP = 35, GLYPH_COUNT = 34;
+constexpr int GLYPH_H = 90, GLYPH_W = 45, GLYPH_TOP = 35;
 constexpr int DOT_H = 70, DOT_W = 10, DOT_TOP = 45, DOT_LEFT = 158;
 constexpr int GLYPH_PIXELS = GLYPH_H * GLYPH_W;
 static_assert(GLYPH_COUNT * GLYPH_PIXELS * 4 + DOT_H * DOT_W * 4 == YOLO_PLATE_GLYPH_BYTES, "the atlas layout of include/yolo_amd.h");
-
-struct PlateRow {                                         // YOLO_PLATE_ROW_WORDS 32-bit words (include/yolo_amd.h)
-    int has;
-    int glyph[7];
-    int l, t, r, b;
-    uint32_t k0, k1;
-    float s;
-    int pad;
-    float m[9];
-    float w0, w1;
-    float A[9], D[9], e[3];
-};
-static_assert(sizeof(PlateRow) == 4 * YOLO_PLATE_ROW_WORDS, "the parameter row is YOLO_PLATE_ROW_WORDS words");
-
-// "no plate": the flag is off, or a glyph id does not name a glyph of the atlas -- then nothing is composed, sampled or blended
-__device__ __forceinline__ bool plate_ok(const PlateRow& R) {
-    bool ok = R.has != 0;
-#pragma unroll
-    for (int k = 0; k < 7; ++k) ok = ok && R.glyph[k] >= 0 && R.glyph[k] < GLYPH_COUNT;
-    return ok;
-}
 
 // the left column of glyph cell k of 7 (LP_GLYPH_X without the dot's entry)
 __device__ __forceinline__ int plate_cell_x(int k) {
@@ -73,28 +51,6 @@ __global__ __launch_bounds__(PLATE_THREADS) void plate_compose_kernel(const uint
     if (y >= DOT_TOP && y < DOT_TOP + DOT_H && x >= DOT_LEFT && x < DOT_LEFT + DOT_W)
         src = GLYPH_COUNT * GLYPH_PIXELS + (y - DOT_TOP) * DOT_W + (x - DOT_LEFT);
     plates[n * (PLATE_H * PLATE_W) + q] = src >= 0 ? glyphs[src] : 0xffffffffu;
-}
-
-// Philox4x32-10 (Salmon et al., SC11; the Random123 constants): counter c[4], key (k0, k1) -> c[4]
-__device__ __forceinline__ void philox4x32_10(uint32_t* c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0;
-        c[1] = lo1;
-        c[2] = n2;
-        c[3] = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-
-// the sum of the 8 bytes of two words, less its mean 1020: an 8-term Irwin-Hall variate, an integer in -1020..1020
-__device__ __forceinline__ float plate_noise_z(uint32_t a, uint32_t b) {
-    const uint32_t t = __builtin_amdgcn_sad_u8(b, 0u, __builtin_amdgcn_sad_u8(a, 0u, 0u));
-    return (float)((int)t - 1020);
 }
 
 // What the pixel kernels need of a row after the checks; plate == nullptr means "no plate".
@@ -133,16 +89,7 @@ __device__ __forceinline__ void plate_quad(const PlateView& v, int j0, int i, fl
         const float* m = v.m;
         const unsigned char* plate = v.plate;
         render_blur_quad(
-            [&](float x, float y, float* val) {
-                const float nx = (m[0] * x + m[1] * y) + m[2];
-                const float ny = (m[3] * x + m[4] * y) + m[5];
-                const float den = (m[6] * x + m[7] * y) + m[8];
-                const bool front = den > 0.f && den < __builtin_huge_valf();       // (false for a NaN)
-                // the tap's addresses are clamped whatever nx / den is, so it is taken anyway and dropped: no divergent branch
-                render_tap(plate, PLATE_H, PLATE_W, nx / den, ny / den, val);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) val[c] = front ? val[c] : 0.f;
-            },
+            [&](float x, float y, float* val) { plate_sample(plate, m, x, y, val); },
             v.w0, v.w1, j0, i, Q);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -158,16 +105,7 @@ __device__ __forceinline__ void plate_quad(const PlateView& v, int j0, int i, fl
     }
     if (v.s != 0.f) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                uint32_t c[4] = {(uint32_t)(j0 + e), (uint32_t)i, (uint32_t)h, 0u};
-                philox4x32_10(c, v.k0, v.k1);
-                const float z0 = plate_noise_z(c[0], c[1]), z1 = plate_noise_z(c[2], c[3]);
-                Q[e][2 * h] = fminf(fmaxf(Q[e][2 * h] + z0 * v.s, 0.f), 255.f);
-                Q[e][2 * h + 1] = fminf(fmaxf(Q[e][2 * h + 1] + z1 * v.s, 0.f), 255.f);
-            }
-        }
+        for (int e = 0; e < 4; ++e) plate_noise(Q[e], j0 + e, i, v.s, v.k0, v.k1);
     }
 }
 

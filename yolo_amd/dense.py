@@ -405,6 +405,11 @@ class OCRNet(DenseNet):
         """(B, W', 1 + classes) float32: score and class logits side by side, as yolo_ocr_decode reads them (a view of the cached
         output: overwritten by the next call with this shape)."""
         self.forward(x)
+        return self.held_logits(x)
+
+    def held_logits(self, x):
+        """The same view WITHOUT running the net: what the last forward pass with x's shape left (PlateReader.read_device has just
+        run it)."""
         lg = self._plans[tuple(x.shape)].logits
         return lg.view(lg.shape[0], lg.shape[2], lg.shape[3])
 

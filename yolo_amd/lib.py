@@ -153,6 +153,12 @@ SIGNATURES = {
     'yolo_dense_transition_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'yolo_dense_bn_relu': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'yolo_ocr_decode': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    'yolo_ocr_plate_workspace_bytes': (_ll, [_i, _i, _i]),
+    'yolo_ocr_plate_blur': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'yolo_ocr_plate_render': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'yolo_ocr_targets': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'yolo_ocr_loss_fwd_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp]),
+    'yolo_ocr_score': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 
 _lib = None

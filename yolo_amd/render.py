@@ -621,6 +621,32 @@ PLATE_GLYPH_BYTES = 34 * 90 * 45 * 4 + 70 * 10 * 4
 PLATE_NOISE_UNIT = math.sqrt(8 * 65535 / 12.0)
 
 
+# the OCR batch (csrc/ocr_data.hip; include/yolo_amd.h, yolo_ocr_plate_blur): per image one plate row whose map is affine, and one
+# row of OCR_TAP_WORDS words for the blur: word 0 T (taps per side, 0..OCR_BLUR_TAPS), words 1..T+1 the float32 weights w[0..T]
+OCR_TAP_WORDS = 32
+OCR_BLUR_TAPS = 24
+# LPGenerator.render's arguments: the reference's call (:181-189) for scale, aspect, R and G; noise is PILImageEnhance's own
+# default (:47-48; the call passes no noise_var); M and N are 0.1 where the call passes 10.0 (see LPGenerator.render)
+OCR_RENDER_DEFAULTS = dict(scale=(0.9, 1.0), aspect=(0.9, 1.1), R=5.0, G=8.0, noise=10.0, M=0.1, N=0.1)
+
+
+def gaussian_taps(sigma):
+    """The tap row of the OCR renderer's blur: a true Gaussian w[k] = exp(-k^2 / (2 sigma^2)), k = 0..T, truncated at
+    T = min(ceil(3 sigma), OCR_BLUR_TAPS) and normalised (in float64) to w[0] + 2 sum w[1..T] = 1; below BLUR_MIN_SIGMA T = 0 and
+    w[0] = 1: no blur.  -> OCR_TAP_WORDS int32 words, the weights stored by bit pattern."""
+    row = np.zeros(OCR_TAP_WORDS, np.int32)
+    fl = row.view(np.float32)
+    if sigma < BLUR_MIN_SIGMA:
+        fl[1] = 1.0
+        return row
+    T = min(int(math.ceil(3.0 * sigma)), OCR_BLUR_TAPS)
+    k = np.arange(T + 1, dtype=np.float64)
+    g = np.exp(-k * k / (2.0 * sigma * sigma))
+    row[0] = T
+    fl[1:T + 2] = (g / (g[0] + 2.0 * g[1:].sum())).astype(np.float32)
+    return row
+
+
 def homography(src, dst):
     """cv2.getPerspectiveTransform(src, dst) (cv2 is absent here): the projective map through four point pairs, as the
     3x3 matrix normalised to M[2, 2] = 1 -- the eight unknowns of  u = (a x + b y + c) / (g x + h y + 1),
@@ -676,6 +702,8 @@ class LPGenerator(object):
         self.dot = Image.open(os.path.join(fonts_dir, '34.png')).resize((10, 70), Image.BILINEAR)
         # (:52-55: augs2 = CreateAugmenter(pca_noise=0.1, brightness=0.7, contrast=0.7, saturation=0.7, hue=1.0))
         self.augs = ColorAugmenter(brightness=0.7, contrast=0.7, saturation=0.7, hue=1.0, pca_noise=0.1) if augment else None
+        # (:50-53: augs = CreateAugmenter(pca_noise=1.0, brightness=0.5, contrast=0.5, saturation=0.3, hue=1.0), render's)
+        self.ocr_augs = ColorAugmenter(brightness=0.5, contrast=0.5, saturation=0.3, hue=1.0, pca_noise=1.0) if augment else None
 
     def draw_LP(self):
         """(:58-77) -> (RGBA plate 380 x 160 on white, type 0, [[glyph id, left, right (fractions of the width)] x 7])."""
@@ -803,6 +831,15 @@ class LPGenerator(object):
             labels[i, 0] = np.asarray([1, X, Y, Z, rot[0], rot[1], rot[2], x, y, 0], np.float32)
         return labels, rows
 
+    def _device(self, dev):
+        """What the device routes keep per device: the glyph atlas, staging buffers, plates and workspaces by batch size."""
+        import torch
+        state = self.__dict__.setdefault('_device_state', {})
+        if state.get('device') != dev:
+            state.clear()
+            state.update(device=dev, atlas=torch.from_numpy(self.glyph_atlas()).to(dev), stage={}, plates={}, work={}, ocr_stage={}, ocr_work={})
+        return state
+
     def add_device(self, imgs, r_max, add_rate=1.0, out=None):
         """add() with the pixels made on the device: imgs (B,3,h,w) float32 0..1 CUDA tensor (RenderCar.render_device's output)
         -> (images with plates, labels (B,1,10)), both on the device.  The host draws the parameter rows (draw_params); rows and
@@ -823,10 +860,7 @@ class LPGenerator(object):
         elif tuple(out.shape) != tuple(imgs.shape) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
             raise ValueError('out should be a contiguous float32 tensor of shape %r on %s' % (tuple(imgs.shape), dev))
         labels, rows = self.draw_params(B, h, w, r_max, add_rate)
-        state = self.__dict__.setdefault('_device_state', {})
-        if state.get('device') != dev:
-            state.clear()
-            state.update(device=dev, atlas=torch.from_numpy(self.glyph_atlas()).to(dev), stage={}, plates={}, work={})
+        state = self._device(dev)
         nrow, nlab = rows.size * 4, labels.size * 4
         slot = state['stage'].get(B)
         if slot is None:
@@ -862,3 +896,212 @@ class LPGenerator(object):
         dev = bg_batch.device
         img = composite(bg_batch, torch.from_numpy(fg).to(dev), torch.from_numpy(mask).to(dev), unit_bg=True)
         return img, torch.from_numpy(labels).to(dev)
+
+    # ---- render (:168-214): the OCR batch -- a plate resized, sheared, rotated, blurred, noised, pasted on a 160 x 384 canvas ---
+    def _ocr_args(self, kw):
+        a = dict(OCR_RENDER_DEFAULTS)
+        unknown = set(kw) - set(a)
+        if unknown:
+            raise TypeError('unknown OCR render arguments: %s' % ', '.join(sorted(unknown)))
+        a.update(kw)
+        return a
+
+    def _ocr_draw(self, h, w, a):
+        """The draws of one image of render(), in its order, up to and including the blur radius (then render() draws the noise
+        field): -> dict(ids, glyph labels, LP_w, LP_h, m, n, deg, sigma)."""
+        ids = [int(g) for g in np.random.randint(10, 34, size=3)]
+        ids += [9 if g == 4 else int(g) for g in np.random.randint(0, 9, size=4)]
+        resize = np.random.uniform(low=a['scale'][0], high=a['scale'][1])
+        LP_w = int(380 * resize)
+        LP_h = int(160 * resize * np.random.uniform(low=a['aspect'][0], high=a['aspect'][1]))
+        m = n = deg = sigma = 0.0
+        if a['M'] > 0 or a['N'] > 0:                              # (yolo_cv.py:106-109, 127)
+            m, n = np.random.random() * a['M'] * 2 - a['M'], np.random.random() * a['N'] * 2 - a['N']
+        if a['R'] != 0:
+            deg = np.random.uniform(low=-a['R'], high=a['R'])
+        if a['G'] != 0:
+            sigma = np.random.rand() * a['G']
+        if int(w - 0.9 * LP_w) <= int(-0.1 * LP_w) or int(h - 0.9 * LP_h) <= int(-0.1 * LP_h):
+            raise ValueError('a %d x %d canvas leaves no paste position for a %d x %d plate' % (h, w, LP_h, LP_w))
+        return dict(ids=ids, LP_w=LP_w, LP_h=LP_h, m=float(m), n=float(n), deg=float(deg), sigma=float(sigma))
+
+    @staticmethod
+    def _ocr_paste(d, h, w):
+        """(:191-192) the paste position, drawn after the plate is made."""
+        return (int(np.random.randint(int(-0.1 * d['LP_w']), int(w - 0.9 * d['LP_w']))),
+                int(np.random.randint(int(-0.1 * d['LP_h']), int(h - 0.9 * d['LP_h']))))
+
+    @staticmethod
+    def ocr_labels(d, paste_x, w):
+        """(:203-209) [[class, left, right]] x 7 as fractions of the canvas width, float32.  As written there: :203 converts the
+        angle to radians although random_rotate has already done so (yolo_cv.py:151), so the formula sees r (pi / 180)^2 -- kept.
+        ONE deliberate correction: the term |m| LP_h / 2, the shear's shift at the plate's mid-height, which the reference leaves
+        out (its labels ignore the shear); it vanishes at M = 0."""
+        r = math.radians(d['deg']) * math.pi / 180
+        offset = paste_x + abs(d['LP_h'] * math.sin(r) / 2) + abs(d['m']) * d['LP_h'] / 2.
+        cols = LP_GLYPH_X[:3] + LP_GLYPH_X[4:]
+        return np.float32([[g, (offset + (c / 380.) * d['LP_w'] * math.cos(r)) / w, (offset + ((c + 45) / 380.) * d['LP_w'] * math.cos(r)) / w]
+                           for g, c in zip(d['ids'], cols)])
+
+    @staticmethod
+    def ocr_geometry(d, paste_x, paste_y):
+        """-> (M (3,3) float64: canvas pixel INDEX -> plate texel INDEX, affine; [l, t, r, b]: the paste rectangle, unclipped).
+        The stages of render() as maps between continuous coordinates (pixel k spans [k, k+1]), composed: canvas -> (less the
+        paste position) the rotated image -> (PIL's rotate, expand=1) the sheared image -> (random_shearing's AFFINE data) the
+        resized plate -> (scale) the 380 x 160 plate.  PIL crops at every stage's image; the composed map does not."""
+        LP_w, LP_h, m, n = d['LP_w'], d['LP_h'], d['m'], d['n']
+        xshift, yshift = abs(m) * LP_h, abs(n) * LP_w
+        w2, h2 = LP_w + int(round(xshift)), LP_h + int(round(yshift))
+        shear = np.array([[1.0, m, -xshift if m > 0 else 0.0], [n, 1.0, -yshift if n > 0 else 0.0], [0.0, 0.0, 1.0]])
+        if d['deg'] != 0:
+            nw, nh, rot = pil_rotate_matrix(w2, h2, d['deg'])
+        else:
+            nw, nh, rot = w2, h2, np.eye(3)
+        half = np.array([[1.0, 0.0, 0.5], [0.0, 1.0, 0.5], [0.0, 0.0, 1.0]])
+        back = np.array([[1.0, 0.0, -paste_x], [0.0, 1.0, -paste_y], [0.0, 0.0, 1.0]])
+        M = np.linalg.inv(half) @ np.diag([380. / LP_w, 160. / LP_h, 1.0]) @ shear @ rot @ back @ half
+        return M, [paste_x, paste_y, paste_x + int(nw), paste_y + int(nh)]
+
+    def ocr_row(self, d, paste_x, paste_y, h, w, key, sigma_noise, color=None):
+        """One parameter row (PLATE_ROW_WORDS int32 words; include/yolo_amd.h, yolo_ocr_plate_blur): the affine map in words
+        16..24, the canvas-clipped paste rectangle as the window, words 25 and 26 unused."""
+        M, win = self.ocr_geometry(d, paste_x, paste_y)
+        row = np.zeros(PLATE_ROW_WORDS, np.int32)
+        fl = row.view(np.float32)
+        row[0] = 1
+        row[1:8] = d['ids']
+        row[8:12] = [min(max(win[0], 0), w), min(max(win[1], 0), h), min(max(win[2], 0), w), min(max(win[3], 0), h)]
+        row[12:14] = np.asarray(key, np.uint32).view(np.int32)
+        fl[14] = np.float32(sigma_noise / PLATE_NOISE_UNIT)
+        fl[16:25] = M.reshape(-1).astype(np.float32)
+        A, D, e = (np.eye(3), np.zeros((3, 3)), np.zeros(3)) if color is None else color
+        fl[27:36], fl[36:45], fl[45:48] = (np.asarray(A, np.float64).reshape(-1).astype(np.float32),
+                                           np.asarray(D, np.float64).reshape(-1).astype(np.float32), np.asarray(e, np.float64).astype(np.float32))
+        return row
+
+    def draw_ocr_params(self, batch, h, w, **kw):
+        """render_host's draws without touching a pixel -> (labels (B,7,3) float32, rows (B, PLATE_ROW_WORDS) int32, taps
+        (B, OCR_TAP_WORDS) int32, orders (B,7) int32: loss_mask's nd.random.shuffle of each image's labels, drawn after the images).
+        Host only.  Per image: three letters, four digits (4 -> 9), resize, aspect, shear m and n, the angle, the blur radius --
+        render_host's draws so far --, then the paste position, TWO uint32 key words where the host route draws a field of normals
+        BEFORE the paste position, then the colour augmenter's draws.  So the first image has render_host's glyphs, sizes, shear,
+        angle and blur; its paste position too when the host's noise field is not drawn from the stream."""
+        a = self._ocr_args(kw)
+        labels = -np.ones((batch, 7, 3), np.float32)
+        rows = np.zeros((batch, PLATE_ROW_WORDS), np.int32)
+        taps = np.zeros((batch, OCR_TAP_WORDS), np.int32)
+        for i in range(batch):
+            d = self._ocr_draw(h, w, a)
+            paste_x, paste_y = self._ocr_paste(d, h, w)
+            key = np.random.randint(0, 2 ** 32, size=2, dtype=np.uint32) if a['noise'] != 0 else (0, 0)
+            color = self.ocr_augs.affine() if self.ocr_augs is not None else None
+            rows[i] = self.ocr_row(d, paste_x, paste_y, h, w, key, a['noise'], color)
+            taps[i] = gaussian_taps(d['sigma'])
+            labels[i] = self.ocr_labels(d, paste_x, w)
+        orders = np.stack([np.random.permutation(7) for _ in range(batch)]).astype(np.int32)
+        return labels, rows, taps, orders
+
+    def render_host(self, batch, h, w, **kw):
+        """The host half of render() (:178-209), with PIL as written: (fg, mask (B,3,h,w) float32, labels (B,7,3))."""
+        from PIL import Image, ImageFilter
+        a = self._ocr_args(kw)
+        fg = np.zeros((batch, 3, h, w), np.float32)
+        mask = np.zeros((batch, 3, h, w), np.float32)
+        labels = -np.ones((batch, 7, 3), np.float32)
+        cols = LP_GLYPH_X[:3] + LP_GLYPH_X[4:]
+        for i in range(batch):
+            d = self._ocr_draw(h, w, a)
+            plate = Image.new('RGBA', (380, 160), (255, 255, 255))
+            for g, c in zip(d['ids'], cols):
+                plate.paste(self.glyph[g], (c, 35))
+            plate.paste(self.dot, (LP_GLYPH_X[3], 45))
+            plate = plate.resize((d['LP_w'], d['LP_h']), Image.BILINEAR)
+            if a['M'] > 0 or a['N'] > 0:                          # random_shearing (yolo_cv.py:120-135)
+                m, n = d['m'], d['n']
+                xshift, yshift = abs(m) * d['LP_h'], abs(n) * d['LP_w']
+                plate = plate.transform((d['LP_w'] + int(round(xshift)), d['LP_h'] + int(round(yshift))), Image.AFFINE,
+                                        (1, m, -xshift if m > 0 else 0, n, 1, -yshift if n > 0 else 0), Image.BILINEAR)
+            if a['R'] != 0:
+                plate = plate.rotate(d['deg'], Image.BILINEAR, expand=1)
+            if a['G'] != 0:
+                plate = plate.filter(ImageFilter.GaussianBlur(radius=d['sigma']))
+            if a['noise'] != 0:
+                px = np.array(plate)
+                plate = Image.fromarray(np.uint8(np.clip(px + np.random.normal(0., a['noise'], px.shape), 0, 255)))
+            paste_x, paste_y = self._ocr_paste(d, h, w)
+            tmp = Image.new('RGBA', (w, h))
+            tmp.paste(plate, (paste_x, paste_y))
+            bands = tmp.split()
+            rgb = np.asarray(Image.merge('RGB', bands[:3]), np.float32)
+            if self.ocr_augs is not None:
+                rgb = self.ocr_augs(rgb)
+            mask[i] = np.asarray(bands[-1], np.float32) / np.float32(255.)
+            fg[i] = rgb.transpose(2, 0, 1) / np.float32(255.)
+            labels[i] = self.ocr_labels(d, paste_x, w)
+        return fg, mask, labels
+
+    def render(self, bg, **kw):
+        """(:168-214) bg (B,3,h,w) float32 0..255 CUDA tensor (BackgroundBank.next_batch's output) -> (images 0..1, labels
+        (B,7,3) [class, left, right]) on the device: the plates drawn with PIL on the host, the blend on the device.
+        Keyword arguments (OCR_RENDER_DEFAULTS): scale, aspect, R, G as the reference's call passes them; noise = 10.0,
+        PILImageEnhance's own default (the call passes no noise_var); M = N = 0.1 where the call passes 10.0 -- as
+        random_shearing stands (yolo_cv.py:120-135) M is a shear FACTOR, so 10.0 smears a plate over up to ten times its height
+        while the labels ignore it; 10.0 can be passed and is rendered faithfully."""
+        import torch
+        B, _, h, w = bg.shape
+        fg, mask, labels = self.render_host(B, h, w, **kw)
+        dev = bg.device
+        return composite(bg, torch.from_numpy(fg).to(dev), torch.from_numpy(mask).to(dev)), torch.from_numpy(labels).to(dev)
+
+    def render_device(self, bg, out=None, **kw):
+        """render() with the pixels made on the device: bg (B,3,h,w) float32 0..255 CUDA tensor -> (images 0..1, labels (B,7,3)),
+        both on the device.  The host draws rows, taps, labels and shuffle orders (draw_ocr_params); they go up in ONE pinned,
+        non-blocking copy; yolo_plate_compose writes the plates, yolo_ocr_plate_blur samples, blurs and noises the paste
+        rectangle and takes the colour sums, yolo_ocr_plate_render colours and blends.  Runs on the current stream and does not
+        synchronise.  out=bg draws in place.  The orders of this call stay on the device as self.ocr_order (B,7) int32, for
+        ocr_targets.  The blur is a true Gaussian of sigma = rand * G truncated at min(ceil(3 sigma), 24) taps -- this library's
+        rule, not PIL's box-blur approximation: the same kind of picture, not the same pixels.  Keyword arguments: see render()."""
+        import torch
+        from . import lib as L
+        lib = L.load()
+        if bg.dim() != 4 or bg.shape[1] != 3 or bg.dtype != torch.float32 or not bg.is_cuda:
+            raise ValueError('bg should be a float32 CUDA tensor of shape (B, 3, h, w)')
+        B, _, h, w = bg.shape
+        dev = bg.device
+        L.require_current_device(dev, 'this render_device call')
+        bg = bg.contiguous()
+        if out is None:
+            out = torch.empty_like(bg)
+        elif tuple(out.shape) != tuple(bg.shape) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+            raise ValueError('out should be a contiguous float32 tensor of shape %r on %s' % (tuple(bg.shape), dev))
+        labels, rows, taps, orders = self.draw_ocr_params(B, h, w, **kw)
+        state = self._device(dev)
+        sizes = [rows.size * 4, taps.size * 4, labels.size * 4, orders.size * 4]
+        ends = np.cumsum(sizes)
+        slot = state['ocr_stage'].get(B)
+        if slot is None:
+            slot = state['ocr_stage'][B] = [torch.empty(int(ends[-1]), dtype=torch.uint8, pin_memory=True), torch.cuda.Event()]
+        else:
+            slot[1].synchronize()         # the previous upload has left the staging buffer (waits for that copy only)
+        host = slot[0].numpy()
+        for part, end, size in zip((rows, taps, labels, orders), ends, sizes):
+            host[end - size:end] = part.reshape(-1).view(np.uint8)
+        up = torch.empty(int(ends[-1]), dtype=torch.uint8, device=dev)
+        up.copy_(slot[0], non_blocking=True)
+        slot[1].record()
+        plates = state['plates'].get(B)
+        if plates is None:
+            plates = state['plates'][B] = torch.empty((B, 160, 380, 4), dtype=torch.uint8, device=dev)
+        work = state['ocr_work'].get((B, h, w))
+        if work is None:
+            nbytes = lib.yolo_ocr_plate_workspace_bytes(B, h, w)
+            if nbytes <= 0:
+                raise L.YoloError('ocr_plate_workspace_bytes failed with status %d' % nbytes)
+            work = state['ocr_work'][(B, h, w)] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        st = L.stream_ptr()
+        taps_d = up[int(ends[0]):int(ends[1])]
+        L.check(lib.yolo_plate_compose(L.ptr(state['atlas']), L.ptr(up), L.ptr(plates), B, st), 'plate_compose')
+        L.check(lib.yolo_ocr_plate_blur(L.ptr(plates), L.ptr(up), L.ptr(taps_d), L.ptr(work), B, h, w, st), 'ocr_plate_blur')
+        L.check(lib.yolo_ocr_plate_render(L.ptr(bg), L.ptr(up), L.ptr(work), L.ptr(out), B, h, w, 0, st), 'ocr_plate_render')
+        self.ocr_order = up[int(ends[2]):int(ends[3])].view(torch.int32).view(B, 7)
+        return out, up[int(ends[1]):int(ends[2])].view(torch.float32).view(B, 7, 3)
