@@ -884,6 +884,51 @@ int yolo_dense_transition_fwd(const void* x, const void* w_image, const float* s
  * (H,1) convolution without padding (the OCR head, OCR/OCR.py:63) is then a 1x1 yolo_conv_fwd with Cin = H*Cp. */
 int yolo_dense_bn_relu(const void* x, const float* scale, const float* bias, void* y, int N, int H, int W, int C, int Cs, int Cp,
                        int columns, int dtype, void* stream);
+/* ---- DenseNet bodies, train-mode forward (csrc/dense_train.hip) --------------------------------------------------------------------
+ * BatchNorm with the BATCH's statistics.  The four entries above are launched unchanged with (scale, bias) pairs folded from batch
+ * statistics, so train and eval mode share their arithmetic; the entries here measure the statistics and fold them.  A block's feature
+ * map is one buffer, a channel's mean and variance are fixed once it is written: every BN1 of a block folds the SAME per-channel
+ * statistics with its own gamma and beta.  Only BN2's statistics (of the bottleneck m, never stored) and the stem's (of the raw 7x7
+ * output) are recomputed.  No backward, no optimiser.
+ * Every statistic is the mean and the BIASED variance over all pixels.  Reductions are deterministic: a block adds its values in double
+ * in a fixed order and writes ONE partial row to `workspace`, a finishing launch of one block adds the rows in a fixed order (double),
+ * var = max(Q / P - mean^2, 0) in double.  No atomics.  workspace: yolo_dense_stats_workspace_bytes(channels) bytes, 8-byte aligned,
+ * channels = the number of channels the call measures; it needs NO zeroing and is left dirty (every row read was written by the same call).
+ * A statistics entry makes two launches (partial rows, finish).  fold != NULL: the finishing launch also folds ONE BatchNorm of fold->C
+ * channels from mean[0, C) / var[0, C) -- AFTER writing its own slice of them, so the BatchNorm may span channels measured by earlier
+ * calls -- with yolo_fold_bn's arithmetic and padded layout (scale = gamma / sqrtf(var + eps), bias = beta - mean * scale, zeros up to
+ * yolo_padded_channels(C)), and, where running_mean / running_var are given (both or neither), updates running = momentum * running +
+ * (1 - momentum) * batch; running_var takes the biased variance, as yolo_bn_train_fwd states for Gluon.  0 <= momentum <= 1, eps > 0.
+ * Validation as above: YOLO_EINVAL for a NULL pointer (fold may be NULL), a non-positive size, an unknown dtype or a malformed fold;
+ * YOLO_EUNSUPPORTED for a shape outside the limits and a buffer of 2^31 bytes or more; nothing is launched on refusal. */
+#define YOLO_DENSE_STATS_ROWS 256
+typedef struct yolo_bn_batch_fold {
+    const float* gamma; const float* beta;          /* C floats each */
+    float* running_mean; float* running_var;        /* C floats each, or both NULL */
+    float* scale; float* bias;                      /* yolo_padded_channels(C) floats each */
+    int C; float eps; float momentum;
+} yolo_bn_batch_fold;
+long long yolo_dense_stats_workspace_bytes(int channels);
+/* The fold alone (one launch): mean, var hold fold->C floats. */
+int yolo_dense_bn_batch_fold(const float* mean, const float* var, const yolo_bn_batch_fold* fold, void* stream);
+/* mean[0, Cm), var[0, Cm) of m = W1 a over the N*H*W pixels, a = round_dtype(max(0, x scale1 + bias1)) over channels [0, Cin) of the block
+ * buffer: m is formed exactly as stage 1 of yolo_dense_layer_fwd forms it (the same operand image, channels >= Cin masked by a select, one
+ * rounding, the same MFMA chain into fp32 accumulators) and is reduced from the accumulators without being stored.  fold: BN2 (C == Cm).
+ * Supported: Cm % 16 == 0, Cm <= 128, Cin >= 8, Cin <= Cs, Cs % 32 == 0, any H, W >= 1.  buf is only read. */
+int yolo_dense_bottleneck_stats(const void* buf, const void* w1_image, const float* scale1, const float* bias1, float* mean, float* var,
+                                void* workspace, const yolo_bn_batch_fold* fold, int N, int H, int W, int Cs, int Cin, int Cm, int dtype,
+                                void* stream);
+/* mean[c0, c0 + n), var[c0, c0 + n) of channels [c0, c0 + n) of an (N,H,W,Cs) buffer, of the values AS STORED (what the next layer reads).
+ * Any c0 >= 0, n >= 1 with c0 + n <= Cs.  No byte of buf and nothing outside [c0, c0 + n) of mean / var is written.  fold: any BatchNorm
+ * over channels [0, C) of the same mean / var arrays (the next layer's BN1, a transition's or the final BN). */
+int yolo_dense_channel_stats(const void* buf, float* mean, float* var, void* workspace, const yolo_bn_batch_fold* fold, int N, int H, int W,
+                             int Cs, int c0, int n, int dtype, void* stream);
+/* mean[0, F0), var[0, F0) of the stem's raw Conv 7x7 s2 p3 output (fp32, before BN) over N*Hc*Wc: per output value the products and the
+ * order of accumulation are yolo_dense_stem_fwd's, so that entry run with the folded pair normalises what was measured.  fold: the stem's
+ * BN (C == F0).  F0 % 8 == 0, F0 <= 64. */
+int yolo_dense_stem_stats(const float* x_nchw, const float* w_oihw, float* mean, float* var, void* workspace, const yolo_bn_batch_fold* fold,
+                          int N, int H, int W, int F0, void* stream);
+
 /* OCR.predict / valid's reading rule (OCR/OCR.py:180-201) on the device (csrc/ocr.hip): logits (N,Wp,1+ncls) float32 ->
  * score (N,Wp) = 1 / (1 + expf(-logit 0)); column i is a PEAK iff s[i] > thr && s[i] > s[i+1] && s[i] > s[i-1] with s[-1] = s[Wp] = 0;
  * codes (N,Wp) = at a peak the first maximum of the ncls class logits (np.argmax of their softmax), -1 elsewhere; count (N) = peaks.

@@ -1,4 +1,5 @@
-"""DenseNet bodies for inference: OCRNet, LPDenseNet and the PlateReader that turns a rectified plate into text.
+"""DenseNet bodies: OCRNet, LPDenseNet (inference, and the train-mode FORWARD with batch-statistic BatchNorm) and the PlateReader that
+turns a rectified plate into text.
 
 The reference's video pipeline publishes the rectified licence plate on /YOLO/clipped_LP; its only subscriber is OCR/OCR.py, which
 resizes the plate to 160x384, runs OCRDenseNet (OCR/OCR.py:34-74) and reads the text off 24 score columns (predict, :180-201).
@@ -11,7 +12,12 @@ _make_transition) is RESTATED HERE FROM RECALL, not copied:
   transition  BN, ReLU, Conv 1x1 no bias C -> C // 2, AvgPool 2x2 s2; after every block but the last
   then        BN, ReLU and the head of the net at hand
 Every arithmetic operation of a forward pass runs in libyolo_amd.so (csrc/dense.hip, csrc/ocr.hip and yolo_conv_fwd for the heads);
-torch owns the memory and the stream.  Inference only: the reference's OCR / LPD training (loss_mask, train_the) is not offered.
+torch owns the memory and the stream.
+
+forward(x, training=True) is the TRAIN-MODE forward (csrc/dense_train.hip): every BatchNorm normalises with the batch's statistics,
+keeps them (net.batch_stats) and updates its running statistics as Gluon does.  The inference kernels run unchanged with (scale, bias)
+pairs folded from batch statistics; the statistics of a block's channels are measured once, as the channels are written.  It serves
+validation losses in train mode and recalibrate_bn.  The backward pass, the optimiser and an OCRTrainer are not offered.
 """
 import ctypes as C
 import math
@@ -125,6 +131,9 @@ def conv3_matrix(w):
     return m.reshape(G, 9 * Cmp)
 
 
+_MOMENTUM = object()       # placeholder of the per-call momentum in a cached argument tuple
+
+
 class _Plan(object):
     def __init__(self):
         self.ops = []          # (name, function, argument tuple without the stream)
@@ -156,6 +165,9 @@ class DenseNet(object):
         self._plans = {}
         self._version = 0
         self._prepared_version = -1
+        self._folds_stale = False     # a training forward has updated the running statistics since the last fold
+        self._train_plans = {}
+        self.batch_stats = {}
         self._lib = L.load()
 
     # ---- parameters ----------------------------------------------------------------------------------------------------------------
@@ -260,22 +272,17 @@ class DenseNet(object):
         P = self.params
         if not P:
             raise L.YoloError('the net has no parameters: call initialize() or load_params()')
-        self._fold('stem', self.F0)
+        self._fold_all()
         for s, n in enumerate(self.block_config):
             cin = self.channels[s][0]
             for k in range(n):
                 pre = 'stage%d.layer%d.' % (s + 1, k)
-                self._fold(pre + 'bn1', cin)
-                self._fold(pre + 'bn2', self.Cm)
                 self._image(pre + 'conv1', P[pre + 'conv1.weight'].reshape(self.Cm, cin))
                 self._image(pre + 'conv2', conv3_matrix(P[pre + 'conv2.weight']))
                 cin += self.G
             if s != len(self.block_config) - 1:
-                self._fold('trans%d.bn' % (s + 1), cin)
                 self._image('trans%d.conv' % (s + 1), P['trans%d.conv.weight' % (s + 1)].reshape(cin // 2, cin))
         cf = self.channels[-1][1]
-        self._fold('final.bn', cf)
-        self._fold('head.bn', HEAD_WIDTH, conv_bias=P['head.conv1.bias'])
         # the head's first convolution over the zero-padded Cp channels that yolo_dense_bn_relu writes
         w, Cp = P['head.conv1.weight'], round_up(cf, 32)
         wpad = torch.zeros((HEAD_WIDTH, Cp) + tuple(w.shape[2:]), dtype=torch.float32, device=self.device)
@@ -287,12 +294,25 @@ class DenseNet(object):
             self._packed_conv('head.conv1', wpad, 3)
         self._packed_conv('head.conv2', P['head.conv2.weight'], 1)
         self._plain_bias('head.conv2.b', P['head.conv2.bias'])
+        self._plain_bias('head.conv1.b', P['head.conv1.bias'])       # the training forward's raw first convolution
         self._prepared_version = self._version
         return self
 
-    def _ensure_prepared(self):
+    def bn_names(self):
+        """[(name, channels)] of every BatchNorm, in network order."""
+        return [(k[:-len('.gamma')], shp[0]) for k, shp in self.shapes.items() if k.endswith('.gamma')]
+
+    def _fold_all(self):
+        """Every BatchNorm folded from its RUNNING statistics: what the inference path reads."""
+        for name, c in self.bn_names():
+            self._fold(name, c, conv_bias=self.params['head.conv1.bias'] if name == 'head.bn' else None)
+        self._folds_stale = False
+
+    def _ensure_prepared(self, folds=True):
         if self._prepared_version != self._version:
             self.prepare()
+        elif folds and self._folds_stale:
+            self._fold_all()
 
     # ---- the launch list of one input shape ------------------------------------------------------------------------------------------
     def _conv_desc(self, plan, x, wname, sbname, y, N, H, W, cin, cout, k, slope, out_f32):
@@ -313,6 +333,7 @@ class DenseNet(object):
         pr = self._prepared
         bufs = [torch.empty((N, h, w, round_up(c1, 32)), dtype=tdt, device=self.device) for (h, w), (_, c1) in zip(maps, self.channels)]
         plan.keep += bufs
+        plan.bufs = bufs
         s, b = pr['stem']
         # (the first argument, the image, is filled in by forward: the caller's tensor is read in place)
         plan.ops.append(('stem', lib.yolo_dense_stem_fwd, (None, L.ptr(self.params['stem.weight']), L.ptr(s), L.ptr(b),
@@ -339,21 +360,36 @@ class DenseNet(object):
     def _head_ops(self, plan, buf, N, h, w):
         raise NotImplementedError
 
-    def _plan(self, x):
+    def _head_front(self, plan, buf, act, mid, N, h, w, conv_hw, conv_cin, k, columns):
+        """The final BN + ReLU into act and the head's first convolution (+ its folded BN + ReLU) into mid; the subclass appends the
+        rest of its head.  plan.head is what the training plan needs to restate these two steps with batch statistics."""
+        lib, dt = self._lib, _LIB_DT[self.dtype]
+        cf = self.channels[-1][1]
+        s, b = self._prepared['final.bn']
+        plan.ops.append(('final.bn', lib.yolo_dense_bn_relu, (L.ptr(buf), L.ptr(s), L.ptr(b), L.ptr(act), N, h, w, cf, buf.shape[3],
+                                                               round_up(cf, 32), columns, dt)))
+        self._conv_desc(plan, act, 'head.conv1', 'head.bn', mid, N, conv_hw[0], conv_hw[1], conv_cin, HEAD_WIDTH, k, 0.0, False)
+        plan.head = dict(act=act, mid=mid, conv_hw=conv_hw, conv_cin=conv_cin, k=k, columns=columns, tail=len(plan.ops))
+
+    def _plan(self, x, folds=True):
         if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32:
             raise ValueError('input must be (B, 3, H, W) float32')
         if not x.is_contiguous() or x.device != self.device:
             # (read in place by the stem kernel: a silent copy would allocate on every call)
             raise ValueError('input must be a contiguous tensor on %s' % self.device)
         L.require_current_device(self.device, 'this DenseNet')
-        self._ensure_prepared()
+        self._ensure_prepared(folds)
         key = tuple(x.shape)
         plan = self._plans.get(key)
         if plan is None:
             plan = self._plans[key] = self._build_plan(x.shape[0], x.shape[2], x.shape[3])
         return plan
 
-    def forward(self, x):
+    def forward(self, x, training=False, momentum=0.9):
+        """training=False: inference with the running statistics.  training=True: BatchNorm with the batch's statistics (see
+        _forward_train); the same output tensors either way."""
+        if training:
+            return self._forward_train(x, momentum)
         plan = self._plan(x)
         st = L.stream_ptr()
         for name, fn, args in plan.ops:
@@ -364,10 +400,150 @@ class DenseNet(object):
 
     __call__ = forward
 
+    # ---- the train-mode forward ------------------------------------------------------------------------------------------------------
+    def _batch_fold(self, tp, name, c, mean, var):
+        """The yolo_bn_batch_fold of BatchNorm `name` over mean[:c] / var[:c]; its (scale, bias) pair is the training plan's own."""
+        P = self.params
+        cp = self._lib.yolo_padded_channels(c)
+        scale = torch.empty(cp, dtype=torch.float32, device=self.device)
+        bias = torch.empty(cp, dtype=torch.float32, device=self.device)
+        d = L.BnBatchFold()
+        d.gamma, d.beta = L.ptr(P[name + '.gamma']), L.ptr(P[name + '.beta'])
+        d.running_mean, d.running_var = L.ptr(P[name + '.running_mean']), L.ptr(P[name + '.running_var'])
+        d.scale, d.bias, d.C, d.eps, d.momentum = L.ptr(scale), L.ptr(bias), c, BN_EPS, 0.9
+        tp.folds.append(d)
+        tp.pairs[name] = (scale, bias)
+        tp.stats[name] = (mean[:c], var[:c])
+        return C.byref(d), scale, bias
+
+    def _build_train_plan(self, plan, N, H, W):
+        """The launch list of one training forward on the buffers and outputs of the inference plan of the same shape.  Per dense
+        layer: the bottleneck's statistics (+ fold of BN2), the unchanged layer kernel, the statistics of the G channels it appended
+        (+ fold of the NEXT BatchNorm over the block's channels: the next layer's BN1, the transition's or the final one)."""
+        lib, dt, dev = self._lib, _LIB_DT[self.dtype], self.device
+        pr, bufs = self._prepared, plan.bufs
+        tp = _Plan()
+        tp.folds, tp.pairs, tp.stats, tp.out, tp.bufs, tp.head = [], {}, {}, plan.out, bufs, plan.head
+        f32 = lambda n: torch.empty(n, dtype=torch.float32, device=dev)
+        widest = max([self.Cm, self.F0, HEAD_WIDTH] + [b.shape[3] for b in bufs])
+        ws = torch.empty(lib.yolo_dense_stats_workspace_bytes(widest), dtype=torch.uint8, device=dev)
+        maps = block_maps(H, W, len(self.block_config))
+        nblocks = len(self.block_config)
+        ops = tp.ops
+
+        def next_bn(si, k):
+            if k + 1 < self.block_config[si]:
+                return 'stage%d.layer%d.bn1' % (si + 1, k + 1)
+            return 'trans%d.bn' % (si + 1) if si != nblocks - 1 else 'final.bn'
+
+        m, v = f32(self.F0), f32(self.F0)
+        fd, s, b = self._batch_fold(tp, 'stem', self.F0, m, v)
+        wstem = L.ptr(self.params['stem.weight'])
+        ops.append(('stem.stats', lib.yolo_dense_stem_stats, (None, wstem, L.ptr(m), L.ptr(v), L.ptr(ws), fd, N, H, W, self.F0)))
+        ops.append(('stem', lib.yolo_dense_stem_fwd, (None, wstem, L.ptr(s), L.ptr(b), L.ptr(bufs[0]), N, H, W, self.F0, bufs[0].shape[3], dt)))
+        for si, n in enumerate(self.block_config):
+            (h, w), buf, cin = maps[si], bufs[si], self.channels[si][0]
+            Cs = buf.shape[3]
+            bm, bv = f32(Cs), f32(Cs)                       # the block's channel statistics: every BN1 of the block is a view of them
+            fd, s1, t1 = self._batch_fold(tp, 'stage%d.layer0.bn1' % (si + 1), cin, bm, bv)
+            ops.append(('stage%d.stats' % (si + 1), lib.yolo_dense_channel_stats, (L.ptr(buf), L.ptr(bm), L.ptr(bv), L.ptr(ws), fd, N, h, w, Cs, 0, cin, dt)))
+            for k in range(n):
+                pre = 'stage%d.layer%d.' % (si + 1, k)
+                m2, v2 = f32(self.Cm), f32(self.Cm)
+                fd, s2, t2 = self._batch_fold(tp, pre + 'bn2', self.Cm, m2, v2)
+                ops.append((pre + 'bn2.stats', lib.yolo_dense_bottleneck_stats,
+                            (L.ptr(buf), L.ptr(pr[pre + 'conv1']), L.ptr(s1), L.ptr(t1), L.ptr(m2), L.ptr(v2), L.ptr(ws), fd, N, h, w, Cs, cin,
+                             self.Cm, dt)))
+                ops.append((pre[:-1], lib.yolo_dense_layer_fwd,
+                            (L.ptr(buf), L.ptr(pr[pre + 'conv1']), L.ptr(s1), L.ptr(t1), L.ptr(pr[pre + 'conv2']), L.ptr(s2), L.ptr(t2),
+                             N, h, w, Cs, cin, self.Cm, self.G, dt)))
+                fd, s1, t1 = self._batch_fold(tp, next_bn(si, k), cin + self.G, bm, bv)
+                ops.append((pre + 'stats', lib.yolo_dense_channel_stats, (L.ptr(buf), L.ptr(bm), L.ptr(bv), L.ptr(ws), fd, N, h, w, Cs, cin, self.G, dt)))
+                cin += self.G
+            if si != nblocks - 1:
+                ops.append(('trans%d' % (si + 1), lib.yolo_dense_transition_fwd,
+                            (L.ptr(buf), L.ptr(pr['trans%d.conv' % (si + 1)]), L.ptr(s1), L.ptr(t1), L.ptr(bufs[si + 1]), N, h, w, cin,
+                             Cs, bufs[si + 1].shape[3], dt)))
+        # the head: final BN + ReLU with the folded pair, the first convolution RAW (scale 1, its bias), yolo_bn_train_fwd in place
+        hd, (h, w), buf, cf = plan.head, maps[-1], bufs[-1], self.channels[-1][1]
+        ops.append(('final.bn', lib.yolo_dense_bn_relu, (L.ptr(buf), L.ptr(s1), L.ptr(t1), L.ptr(hd['act']), N, h, w, cf, buf.shape[3],
+                                                          round_up(cf, 32), hd['columns'], dt)))
+        ch, cw = hd['conv_hw']
+        self._conv_desc(tp, hd['act'], 'head.conv1', 'head.conv1.b', hd['mid'], N, ch, cw, hd['conv_cin'], HEAD_WIDTH, hd['k'], 1.0, False)
+        hm, hv, hinv = f32(HEAD_WIDTH), f32(HEAD_WIDTH), f32(HEAD_WIDTH)
+        tp.stats['head.bn'], tp.head_invstd = (hm, hv), hinv
+        ops.append(('head.bn.stats', lib.yolo_dense_channel_stats, (L.ptr(hd['mid']), L.ptr(hm), L.ptr(hv), L.ptr(ws), None, N, ch, cw, HEAD_WIDTH,
+                                                                     0, HEAD_WIDTH, dt)))
+        bnws = torch.zeros(2 * HEAD_WIDTH, dtype=torch.float64, device=dev)          # zero on entry, left zero by every call
+        hmean = f32(HEAD_WIDTH)
+        P = self.params
+        ops.append(('head.bn', lib.yolo_bn_train_fwd,
+                    (L.ptr(hd['mid']), L.ptr(P['head.bn.gamma']), L.ptr(P['head.bn.beta']), None, L.ptr(hd['mid']), L.ptr(hmean), L.ptr(hinv),
+                     L.ptr(P['head.bn.running_mean']), L.ptr(P['head.bn.running_var']), L.ptr(bnws), N * ch * cw, HEAD_WIDTH, BN_EPS,
+                     _MOMENTUM, 0.0, dt)))
+        ops += plan.ops[hd['tail']:]
+        tp.keep += [ws, bnws, hmean, plan]
+        return tp
+
+    def _train_plan(self, x):
+        plan = self._plan(x, folds=False)                    # (the running statistics are not read: no re-fold for a training call)
+        tp = self._train_plans.get(tuple(x.shape))
+        if tp is None or tp.version != self._prepared_version:       # (a plan holds pointers to the parameters it was built with)
+            tp = self._train_plans[tuple(x.shape)] = self._build_train_plan(plan, x.shape[0], x.shape[2], x.shape[3])
+            tp.version = self._prepared_version
+        return tp
+
+    def _forward_train(self, x, momentum):
+        """One forward pass with batch statistics.  Every BatchNorm's running statistics in `params` are updated in place (running =
+        momentum * running + (1 - momentum) * batch, the biased variance: Gluon) and the net is marked for re-folding, so the next
+        inference call folds the updated statistics.  net.batch_stats = {bn name: (mean, var)} float32 device tensors for every
+        BatchNorm of dense_param_shapes (the BN1 entries of one block are views of one array): the state a backward pass reads,
+        OVERWRITTEN by the next training call with this input shape.  Nothing is allocated after the first such call."""
+        momentum = float(momentum)
+        if not 0.0 <= momentum <= 1.0:
+            raise ValueError('momentum must lie in [0, 1]')
+        tp = self._train_plan(x)
+        for d in tp.folds:
+            d.momentum = momentum
+        st, xp = L.stream_ptr(), L.ptr(x)
+        for name, fn, args in tp.ops:
+            if args[0] is None:
+                args = (xp,) + args[1:]
+            elif name == 'head.bn':
+                args = tuple(momentum if a is _MOMENTUM else a for a in args)
+            L.check(fn(*args, st), name)
+        self._folds_stale = True
+        self.batch_stats = tp.stats
+        return tp.out
+
+    def training_buffers(self, x):
+        """For the tests' stage-by-stage comparison: what the last training (or inference) forward with x's shape left in the block
+        buffers [(N, h, w, Cs)], the head's activated input and its hidden map."""
+        plan = self._plans[tuple(x.shape)]
+        return dict(blocks=plan.bufs, act=plan.head['act'], mid=plan.head['mid'])
+
+    def recalibrate_bn(self, batches):
+        """Re-estimates every BatchNorm's running statistics on `batches` (an iterable of input tensors): the training forward on
+        each, the k-th at momentum 1 - 1 / k, so that the running statistics end as the plain average of the batches' statistics
+        (the first batch replaces what was loaded).  Weights, gamma and beta are untouched.  Returns the number of batches."""
+        k = 0
+        for x in batches:
+            k += 1
+            self._forward_train(x, 1.0 - 1.0 / k)
+        if k == 0:
+            raise ValueError('recalibrate_bn needs at least one batch')
+        return k
+
     @property
     def launches(self):
         """Kernel launches of one forward pass (the same for every input shape)."""
         return 1 + sum(self.block_config) + (len(self.block_config) - 1) + self._head_launches
+
+    @property
+    def train_launches(self):
+        """Kernel launches of one training forward: a statistics entry is two (partial rows, finish + fold), yolo_bn_train_fwd three.
+        Stem 3 + 2, a dense layer 2 + 1 + 2, a transition 1 + 2, the head's BatchNorm 2 + 3 more than in inference."""
+        return 5 + 5 * sum(self.block_config) + 3 * (len(self.block_config) - 1) + self._head_launches + 5
 
 
 class OCRNet(DenseNet):
@@ -394,17 +570,15 @@ class OCRNet(DenseNet):
         mid = torch.empty((N, 1, w, HEAD_WIDTH), dtype=tdt, device=self.device)
         logits = torch.empty((N, 1, w, nout), dtype=torch.float32, device=self.device)
         plan.keep += [cols, mid, logits]
-        s, b = self._prepared['final.bn']
-        plan.ops.append(('final.bn', lib.yolo_dense_bn_relu, (L.ptr(buf), L.ptr(s), L.ptr(b), L.ptr(cols), N, h, w, cf, buf.shape[3], Cp, 1, dt)))
-        self._conv_desc(plan, cols, 'head.conv1', 'head.bn', mid, N, 1, w, h * Cp, HEAD_WIDTH, 1, 0.0, False)
+        self._head_front(plan, buf, cols, mid, N, h, w, (1, w), h * Cp, 1, 1)
         self._conv_desc(plan, mid, 'head.conv2', 'head.conv2.b', logits, N, 1, w, HEAD_WIDTH, nout, 1, 1.0, True)
         plan.logits = logits
         plan.out = [logits[..., :1], logits[..., 1:]]
 
-    def logits(self, x):
+    def logits(self, x, training=False, momentum=0.9):
         """(B, W', 1 + classes) float32: score and class logits side by side, as yolo_ocr_decode reads them (a view of the cached
-        output: overwritten by the next call with this shape)."""
-        self.forward(x)
+        output: overwritten by the next call with this shape).  training=True: the train-mode forward (DenseNet.forward)."""
+        self.forward(x, training, momentum)
         return self.held_logits(x)
 
     def held_logits(self, x):
@@ -433,9 +607,7 @@ class LPDenseNet(DenseNet):
         nhwc = torch.empty((N, h, w, nout), dtype=torch.float32, device=self.device)
         out = torch.empty((N, nout, h, w), dtype=torch.float32, device=self.device)
         plan.keep += [act, mid, nhwc, out]
-        s, b = self._prepared['final.bn']
-        plan.ops.append(('final.bn', lib.yolo_dense_bn_relu, (L.ptr(buf), L.ptr(s), L.ptr(b), L.ptr(act), N, h, w, cf, buf.shape[3], Cp, 0, dt)))
-        self._conv_desc(plan, act, 'head.conv1', 'head.bn', mid, N, h, w, Cp, HEAD_WIDTH, 3, 0.0, False)
+        self._head_front(plan, buf, act, mid, N, h, w, (h, w), Cp, 3, 0)
         self._conv_desc(plan, mid, 'head.conv2', 'head.conv2.b', nhwc, N, h, w, HEAD_WIDTH, nout, 1, 1.0, True)
         plan.ops.append(('nchw', lib.yolo_nhwc_to_nchw, (L.ptr(nhwc), L.ptr(out), N, nout, h, w, L.F32)))
         plan.out = out

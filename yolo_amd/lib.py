@@ -49,6 +49,12 @@ class ConvDesc(C.Structure):
                 ('x_lo_offset', C.c_longlong), ('y_lo_offset', C.c_longlong)]
 
 
+class BnBatchFold(C.Structure):
+    """yolo_bn_batch_fold: one BatchNorm folded from batch statistics by a finishing launch of csrc/dense_train.hip."""
+    _fields_ = [('gamma', C.c_void_p), ('beta', C.c_void_p), ('running_mean', C.c_void_p), ('running_var', C.c_void_p),
+                ('scale', C.c_void_p), ('bias', C.c_void_p), ('C', C.c_int), ('eps', C.c_float), ('momentum', C.c_float)]
+
+
 class GridDesc(C.Structure):
     _fields_ = [('nscale', C.c_int), ('A', C.c_int), ('img_h', C.c_int), ('img_w', C.c_int),
                 ('gh', C.c_int * 4), ('gw', C.c_int * 4), ('step', C.c_int * 4),
@@ -152,6 +158,11 @@ SIGNATURES = {
     'yolo_dense_stem_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'yolo_dense_transition_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'yolo_dense_bn_relu': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'yolo_dense_stats_workspace_bytes': (_ll, [_i]),
+    'yolo_dense_bn_batch_fold': (_i, [_vp, _vp, C.POINTER(BnBatchFold), _vp]),
+    'yolo_dense_bottleneck_stats': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(BnBatchFold), _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'yolo_dense_channel_stats': (_i, [_vp, _vp, _vp, _vp, C.POINTER(BnBatchFold), _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'yolo_dense_stem_stats': (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(BnBatchFold), _i, _i, _i, _i, _vp]),
     'yolo_ocr_decode': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     'yolo_ocr_plate_workspace_bytes': (_ll, [_i, _i, _i]),
     'yolo_ocr_plate_blur': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
