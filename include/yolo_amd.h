@@ -129,7 +129,8 @@ typedef struct yolo_conv_desc {
     long long y_batch_stride; /* elements between images in y; 0 = dense Ho*Wo*Cout           */
     long long y_pixel_stride; /* elements between pixels in y; 0 = dense Cout                 */
     int algo;              /* 0 = library heuristic; 1 = generic kernel; >= 2 = a specific pipelined
-                              tile variant (csrc/conv_pipe.hip), YOLO_EUNSUPPORTED if not eligible    */
+                              tile variant (csrc/conv_pipe.hip; 13 / 14: csrc/conv_stream.hip, 30-35: csrc/conv_sk.hip,
+                              43: csrc/conv_flat.hip), YOLO_EUNSUPPORTED if not eligible              */
     long long x_pixel_stride; /* elements between pixels in x; 0 = dense Cin.  > Cin: x is a channel slice of a wider
                               NHWC buffer (the route half of a concat buffer, car/utils.py:93); images stay
                               H*W*x_pixel_stride apart.  The pitch in BYTES must stay below 2^31
@@ -187,6 +188,11 @@ int yolo_conv_stats_rows(const yolo_conv_desc* d);
 /* Name of the kernel instantiation yolo_conv_fwd would launch for `d` (as rocprofv3 prints it);
  * used by bench.py to attribute measured time to the dominant kernel.  Host-only, no launch. */
 int yolo_conv_kernel_name(const yolo_conv_desc* d, char* buf, int len);
+/* algo 43 (csrc/conv_flat.hip): the persistent 1x1 over the flat pixel index -- YOLO_BF16 / YOLO_F16, Cin -> Cout in
+ * {256 -> 128, 512 -> 256}, dense x, y and residual, no out_f32 / upsample2x / stats / tail (YOLO_EUNSUPPORTED otherwise);
+ * bit-identical to the tiled 1x1 variants.  Its tile size in pixels and the resident blocks per compute unit its grid is
+ * sized with: grid = min(ceil(N*H*W / tile_px), compute units * blocks_per_cu).  Host-only, no launch. */
+int yolo_conv_flat_geometry(int Cin, int Cout, int* tile_px, int* blocks_per_cu);
 
 /* The network's first _conv2d (basic_yolo.py:20) fused with the image layout change: Conv3x3 s1 p1 over
  * the (N,3,H,W) float32 NCHW image exactly as the reference feeds it (car/YOLO.py:381) + folded BN +

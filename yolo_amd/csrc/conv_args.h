@@ -96,3 +96,5 @@ int conv_pipe_dispatch(ConvArgs& a, int ks, int stride, int dtype, int algo, hip
 int conv_sk_dispatch(ConvArgs& a, int ks, int stride, int dtype, int algo, hipStream_t st, const NameOut* nm);
 // conv_stream.hip: weights-stationary streaming kernel for the small-channel layers (algo 13 / 14).
 int conv_stream_dispatch(const ConvArgs& a, int ks, int stride, int dtype, int algo, hipStream_t st, const NameOut* nm);
+// conv_flat.hip: persistent weights-stationary 1x1 over the flat pixel index, dense 256 -> 128 / 512 -> 256 maps (algo 43).
+int conv_flat_dispatch(const ConvArgs& a, int ks, int stride, int dtype, hipStream_t st, const NameOut* nm);

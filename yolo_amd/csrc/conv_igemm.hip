@@ -513,6 +513,7 @@ static int conv_dispatch(const yolo_conv_desc* d, void* stream, const NameOut* n
         a.buf32 = (yb < lim && rbytes < lim && tb < lim) ? conv_buf32_form() : 0;
     }
     { static const int lab = (int)YOLO_LAB_ENV("YOLO_EPI_AB", 0); a.lab = lab; }
+    if (d->algo == 43) return conv_flat_dispatch(a, d->ksize, d->stride, d->dtype, st, nm);      // (refuses a tail, statistics, strided views itself)
     if (a.t_wp) {
         // fused tail 1x1: pipelined 3x3 variants with 256-cout tiles only (conv_pipe.hip)
         if (!d->tail_y || (!d->tail_scale != !d->tail_bias) || d->tail_cout <= 0 || !(d->tail_slope >= 0.f && d->tail_slope <= 1.f)) return YOLO_EINVAL;

@@ -76,6 +76,7 @@ SIGNATURES = {
     'yolo_conv_fwd': (_i, [C.POINTER(ConvDesc), _vp]),
     'yolo_conv_kernel_name': (_i, [C.POINTER(ConvDesc), C.c_char_p, _i]),
     'yolo_conv_stats_rows': (_i, [C.POINTER(ConvDesc)]),
+    'yolo_conv_flat_geometry': (_i, [_i, _i, _vp, _vp]),
     'yolo_stem_conv_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp]),
     'yolo_stem_stats_rows': (_i, [_i, _i, _i, _i]),
     'yolo_stem_conv_fwd_stats': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp]),
@@ -204,6 +205,20 @@ def load():
                         'yolo_amd.lib.build())' % (LIB_PATH, got, ABI_VERSION))
     _lib = lib
     return lib
+
+
+CONV_FLAT_ALGO = 43        # yolo_conv_desc.algo of the flat streaming 1x1 (csrc/conv_flat.hip)
+
+
+def conv_flat_geometry(cin, cout):
+    """(tile_px, blocks_per_cu) of algo CONV_FLAT_ALGO for a channel pair, or None when it does not take the pair (host only):
+    its grid is min(ceil(N * H * W / tile_px), compute units * blocks_per_cu) persistent blocks."""
+    tp, bpc = C.c_int(), C.c_int()
+    rc = load().yolo_conv_flat_geometry(cin, cout, C.addressof(tp), C.addressof(bpc))
+    if rc == EUNSUPPORTED:
+        return None
+    check(rc, 'yolo_conv_flat_geometry')
+    return tp.value, bpc.value
 
 
 def check(rc, what):

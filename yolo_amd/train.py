@@ -315,6 +315,10 @@ class Trainer(object):
             # raw convolution: identity epilogue
             d = self._conv_desc(xin.val, xin.shape, self._prep[c.name].wp, None, None, yraw.val, Cc, c.cout, c.k, c.stride)
             d.algo = self._algo(d)
+            if d.algo == L.CONV_FLAT_ALGO and self._fuse_fwd:
+                # an inference choice of the same shape: the flat 1x1 has no statistics epilogue -- the step keeps the tiled 1x1 the
+                # plans held for these shapes before it (same conv bytes), so that the batch sums stay in the convolution
+                d.algo = 39
             op = dict(kind='conv_bn', c=c, x=xin, yraw=yraw, z=z, mean=mean, invstd=invstd, res=residual, desc=d, srows=0)
             if self.split:
                 # the plan owns every gradient buffer of the split path: d(loss)/d(yraw) and, for a stride-2 conv, its dilated copy
