@@ -187,6 +187,61 @@ def test_channel_stats_cancellation(lib, cuda):
     assert ev <= 1e-3 and em <= 1e-6
 
 
+def _cancellation(what, mean, var, y64):
+    """The bars of test_channel_stats_cancellation, per channel, against the float64 statistics of y64 (N, C, H, W); prints what it saw."""
+    m64, v64 = TR.stats(y64)
+    rho = float((m64 * m64 / v64).min())
+    em = float(((mean.double().cpu() - m64).abs() / m64.abs()).max())
+    ev = float(((var.double().cpu() - v64).abs() / v64).max())
+    print('%s cancellation: rho >= %.2e   relative errors mean %.3e var %.3e' % (what, rho, em, ev))
+    assert rho >= 1e5, 'the case is not ill-conditioned'
+    assert ev <= 1e-3 and em <= 1e-6
+
+
+def test_bottleneck_stats_cancellation(lib, cuda):
+    """The bottleneck's output 50 + 0.07 noise per channel (rho about 5e5) over 40 000 pixels: input channel 0 is 1 behind an identity
+    BN1, its weights are 50, the other weights are small."""
+    N, H, W, cin, cm, g = 2, 100, 200, 32, 48, 12
+    Cs = D.round_up(cin + g, 32) + 32
+    gen = torch.Generator().manual_seed(78)
+    x = torch.randn((N, cin, H, W), generator=gen)
+    x[:, 0] = 1.0
+    w = 0.1 * torch.randn((cm, cin), generator=gen) / cin ** 0.5
+    w[:, 0] = 50.0
+    flat, buf = guarded((N, H, W, Cs), torch.float32, cuda)
+    buf[..., :cin] = x.permute(0, 2, 3, 1).to(cuda)
+    cp = lib.yolo_padded_channels(cin)
+    s1, t1 = torch.ones(cp, device=cuda), torch.zeros(cp, device=cuda)
+    w1 = D.pack_operand(w.to(cuda), torch.float32)
+    fm, mean = nan_vec(cm, cuda)
+    fv, var = nan_vec(cm, cuda)
+    fw, ws = workspace(lib, cm, cuda)
+    assert lib.yolo_dense_bottleneck_stats(L.ptr(buf), L.ptr(w1), L.ptr(s1), L.ptr(t1), L.ptr(mean), L.ptr(var), L.ptr(ws), None, N, H, W, Cs,
+                                           cin, cm, L.F32, L.stream_ptr()) == 0
+    torch.cuda.synchronize()
+    assert guards_intact(fm) and guards_intact(fv) and guards_intact(fw)
+    y64 = torch.nn.functional.conv2d(torch.relu(x.double()), w.double().view(cm, cin, 1, 1))
+    _cancellation('bottleneck', mean, var, y64)
+
+
+def test_stem_stats_cancellation(lib, cuda):
+    """A flat image 0.5 + 0.002 noise through a stem whose weight sits on the centre tap (taps summing to 2..6 per channel, the rest
+    5e-4 noise, so that the padded border stays flat too): rho of the raw output about 1e6."""
+    N, H, W, f0 = 2, 100, 200, 16
+    gen = torch.Generator().manual_seed(79)
+    x = 0.5 + 0.002 * (torch.rand((N, 3, H, W), generator=gen) - 0.5)
+    w = 5e-4 * torch.randn((f0, 3, 7, 7), generator=gen)
+    w[:, :, 3, 3] += ((2.0 + 4.0 * torch.rand(f0, generator=gen)) / 3.0)[:, None]
+    xd, wd = x.to(cuda), w.to(cuda).contiguous()
+    fm, mean = nan_vec(f0, cuda)
+    fv, var = nan_vec(f0, cuda)
+    fw, ws = workspace(lib, f0, cuda)
+    assert lib.yolo_dense_stem_stats(L.ptr(xd), L.ptr(wd), L.ptr(mean), L.ptr(var), L.ptr(ws), None, N, H, W, f0, L.stream_ptr()) == 0
+    torch.cuda.synchronize()
+    assert guards_intact(fm) and guards_intact(fv) and guards_intact(fw)
+    _cancellation('stem', mean, var, torch.nn.functional.conv2d(x.double(), w.double(), stride=2, padding=3))
+
+
 # ---- yolo_dense_stem_stats -------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('f0,hw', [(16, (21, 37)), (32, (70, 44)), (64, (22, 19))])
 def test_stem_stats(lib, cuda, f0, hw):

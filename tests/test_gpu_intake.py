@@ -3,6 +3,8 @@ for bit (w is exactly 1 and every operation is IEEE and uncontracted), the ident
 leaves the frame (border 0), rectify_plates on a known answer, and FrameIntake feeding the micro net.
 
 Every comparison prints its observed maximum before it asserts (pytest -s)."""
+import gc
+
 import numpy as np
 import pytest
 import torch
@@ -185,6 +187,9 @@ def test_frame_intake_buffers_sources_and_white_balance(cuda, micro):
     assert np.array_equal(got_a, ref) and np.array_equal(got_b, ref) and np.array_equal(got_c, ref)
     # a second host call reuses the staging buffers: nothing is allocated once the batch size has been seen
     other = frames[::-1].copy()
+    # (cyclic garbage of earlier tests -- the nets of the test above -- holds device memory until the collector runs; collected here,
+    #  so that a collection landing inside the call cannot free it there and pass for, or hide, an allocation of the call's own)
+    gc.collect()
     before = torch.cuda.memory_allocated(cuda)
     d = intake(other)
     assert torch.cuda.memory_allocated(cuda) == before and d.data_ptr() == ptr
