@@ -1,5 +1,5 @@
-// Kernel argument block and host helpers shared by the generic (conv_igemm.hip) and pipelined
-// (conv_pipe.hip) implicit-GEMM convolutions.
+// Kernel argument block and host helpers shared by the convolution units: the dispatcher (conv_dispatch.hip) fills a ConvArgs
+// from a yolo_conv_desc and hands it to one unit's conv_*_dispatch below.
 #pragma once
 #include "common.h"
 
@@ -32,7 +32,8 @@ struct ConvArgs {
     int TWt, nstrips, tiles_per_strip, PW, total_i;
     int row_swz, TP;            // conv_pipe 3x3 stride 1: halo pitch TWt + 4 and a row-relative unit swizzle (see launch_pipe); TP = PW - 4 * row_swz (stride 2: (PW - TWt) / 4)
     int halo_strict;        // conv_pipe.hip launch_pipe: leave one slot of the staged halo unused (the 2x2-window 4-wave tile)
-    int tile_px;            // conv_igemm.hip: strip pixels a tile covers (= its 128 unless the shape needs row-limited tiles); 0 elsewhere
+    int tile_px;            // conv_igemm.hip launch_cfg sets and reads it: strip pixels a tile covers (= its 128 unless the shape needs
+                            // row-limited tiles); the other units leave the dispatcher's 0 and do not read it
     int nchunks, tiles_c;
     int buf32;              // conv_epilogue.h: 1 = y, the residual (and stats_y, tail_y) extents fit 31-bit byte offsets: the epilogue's
                             // loads / stores are unconditional buffer accesses (out-of-range offset = no access)
@@ -90,6 +91,9 @@ static inline int conv_halo_slots(int BP, int d, int Ho, int H, int S, long long
     return (int)(NR * PW);
 }
 
+// Every unit: YOLO_EUNSUPPORTED if it has no kernel for the shape, element type or id (the dispatcher's cue to try the next).
+// conv_igemm.hip: the generic kernel (algo 1), every element type.
+int conv_igemm_dispatch(ConvArgs& a, int ks, int stride, int dtype, hipStream_t st, const NameOut* nm);
 // conv_pipe.hip: pipelined variants (algo >= 2); YOLO_EUNSUPPORTED if the shape is not eligible.
 int conv_pipe_dispatch(ConvArgs& a, int ks, int stride, int dtype, int algo, hipStream_t st, const NameOut* nm);
 // conv_sk.hip: 1x1 with the K range split over the waves of one block (algo 30-35); YOLO_EUNSUPPORTED if not eligible.

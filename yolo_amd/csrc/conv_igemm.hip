@@ -369,277 +369,14 @@ static int launch_dtype(ConvArgs& a, int ks, int stride, hipStream_t st, const N
     return launch_shape<T, 2, 2, 1, 2>(a, ks, stride, st, nm);                    // 128 px x  64 cout
 }
 
-// conv_epilogue.h form: 1 = unconditional buffer accesses (the default), 0 = the branching form (also what extents beyond 31 bits
-// get).  Lab knob: YOLO_NO_BUF32 -> 0.
-static int conv_buf32_form() {
-    static const int v = YOLO_LAB_SET("YOLO_NO_BUF32") ? 0 : 1;
-    return v;
-}
-
-static int conv_dispatch(const yolo_conv_desc* d, void* stream, const NameOut* nm);
-
-// Heuristic choice of the pipelined variant for algo == 0 (1 = stay on the generic kernel): minimise
-// rounds x tile work, where rounds = ceil(tiles / (256 CUs x resident blocks per CU)) -- at the
-// reference's batch sizes tile quantisation on the 13x13 / 26x26 maps costs more than any difference
-// between the variants' inner loops.  The per-variant factors are measured (tools/conv_bench.py).
-static int conv_auto_algo(const ConvArgs& a, int ks, int stride, int dtype, bool px_heavy = true) {
-    if ((!dtype_split(dtype) && (a.Cin * elem_size(dtype)) % 64) || (ks == 1 && a.nchunks < 2)) return 1;      // (split planes are padded to whole chunks)
-    if (dtype_split(dtype)) {
-        // split types (round 6, measured at 416x416 bs 32, tools/layer_times.py --dtype bf16x3): the first stages' narrow layers are not
-        // covered by fused / streaming kernels there -- the 64-cout tiles for them (1x1 64 -> 32 at 208^2: 129 us against 567 on a
-        // 256-cout tile), the generic kernel for the large-map stride-2 layers (32 -> 64 at 416^2: 432 us against 602)
-        if (ks == 1 && a.Cout <= 64) return 40;
-        if (ks == 3 && stride == 1 && a.Cout <= 64) return 41;
-        if (ks == 3 && stride == 2 && a.Cin <= 64) return 1;
-    }
-    if (stride == 2) return ks == 3 ? (a.Cout > 128 ? 18 : 9) : 1;      // (18 = 10 with the 4-slot weight ring)
-    struct V { int algo, bp, bc, bpc; float f; bool k1; };
-    // (round 5: the pixel-heavy 3x3 tiles 27 / 28 -- ~40 % less L2 -> LDS weight stream per output, measured 0.5-3.4 % faster than
-    //  6 / 2 wherever they fill the chip, tools/ab_tiles.sh)
-    static const V vs[] = {{2, 256, 256, 1, 1.00f, true}, {3, 256, 128, 1, 1.10f, true}, {4, 128, 128, 2, 1.05f, true},
-                           {6, 192, 256, 1, 1.00f, false}, {8, 192, 128, 2, 1.05f, true},
-                           {27, 384, 128, 1, 0.98f, false}, {28, 512, 128, 1, 0.97f, false}};
-    const long long px = (long long)a.N * a.Ho * a.Wo;
-    int best = 1;
-    double best_cost = 1e30;
-    for (const V& v : vs) {
-        if (ks == 1 && !v.k1) continue;
-        if (!px_heavy && v.algo >= 27) continue;
-        const long long tiles = ((px + v.bp - 1) / v.bp) * ((a.Cout + v.bc - 1) / v.bc);
-        const long long slots = 256LL * v.bpc;
-        // full rounds keep every CU's bpc block slots busy (the co-resident blocks share the CU: bpc block times); the last,
-        // partial round puts ceil(rest / 256) blocks on the busiest CU -- a launch of fewer tiles than CUs runs one block per CU
-        // at full speed whatever bpc is (13^2 512 -> 1024 at batch 32: 232 tiles of the two-per-CU 192 x 128 tile beat 120 of
-        // the 384 x 128 one, 50.7 against 64.2 us)
-        const long long full = tiles / slots, rest = tiles - full * slots;
-        const double cost = (double)(full * v.bpc + (rest + 255) / 256) * v.bp * v.bc * v.f;
-        if (cost < best_cost) { best_cost = cost; best = v.algo; }
-    }
-    return best;
-}
-
-extern "C" int yolo_conv_fwd(const yolo_conv_desc* d, void* stream) { return conv_dispatch(d, stream, nullptr); }
-
-extern "C" int yolo_conv_kernel_name(const yolo_conv_desc* d, char* buf, int len) {
-    if (!buf || len < 16) return YOLO_EINVAL;
-    NameOut nm{buf, len, nullptr};
-    return conv_dispatch(d, nullptr, &nm);
-}
-
-// Number of partial rows ([rows][2][yolo_padded_channels(Cout)] float32) yolo_conv_fwd writes into d->stats for this
-// descriptor, or YOLO_EUNSUPPORTED when the kernel it would run has no statistics epilogue.  Host-only, no launch
-// (d->stats only has to be non-NULL).
-extern "C" int yolo_conv_stats_rows(const yolo_conv_desc* d) {
-    if (!d || !d->stats) return YOLO_EINVAL;
-    char buf[256];
-    int rows = -1;
-    NameOut nm{buf, (int)sizeof(buf), &rows};
-    const int rc = conv_dispatch(d, nullptr, &nm);
-    if (rc != YOLO_OK) return rc;
-    return rows > 0 ? rows : YOLO_EUNSUPPORTED;
-}
-
-static int conv_dispatch(const yolo_conv_desc* d, void* stream, const NameOut* nm) {
-    if (!d || !d->x || !d->w_packed || !d->y || (!d->scale != !d->bias)) return YOLO_EINVAL;      // (both NULL: identity epilogue)
-    if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0) return YOLO_EINVAL;
-    if (d->ksize != 1 && d->ksize != 3) return YOLO_EUNSUPPORTED;
-    if (d->stride != 1 && d->stride != 2) return YOLO_EUNSUPPORTED;
-    if (d->ksize == 1 && d->stride != 1) return YOLO_EUNSUPPORTED;
-    if (!dtype_valid(d->dtype)) return YOLO_EINVAL;
-    if (!(d->slope >= 0.f && d->slope <= 1.f)) return YOLO_EINVAL;       // LeakyReLU is computed as max(t, t*slope)
-    const int es = elem_size(d->dtype);
-    const bool split = dtype_split(d->dtype);                         // (YOLO_BF16X3: common.h)
-    const int planes = dtype_planes(d->dtype);
-    if ((d->Cin * es) % 16) return YOLO_EUNSUPPORTED;                 // 16-byte K units
-    if (!d->out_f32 && (d->Cout % 4)) return YOLO_EUNSUPPORTED;       // 4-channel store groups
-    if (split && (d->stats || d->tail_w_packed || (!d->out_f32 && (d->Cout % 8)))) return YOLO_EUNSUPPORTED;
-    // split tensors: each plane of a pixel is padded to whole 32-channel K-chunks (include/yolo_amd.h); the pad channels read zeros
-    const int cin_p = split ? round_up(d->Cin, 32) : d->Cin, cout_p = (split && !d->out_f32) ? round_up(d->Cout, 32) : d->Cout;
-    const int pad = d->ksize / 2;
-    ConvArgs a;
-    a.x = (const char*)d->x;
-    a.wp = (const char*)d->w_packed;
-    a.scale = d->scale;
-    a.bias = d->bias;
-    a.res = (const char*)d->residual;
-    a.y = (char*)d->y;
-    a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout;
-    a.Ho = (d->H + 2 * pad - d->ksize) / d->stride + 1;
-    a.Wo = (d->W + 2 * pad - d->ksize) / d->stride + 1;
-    a.Cout_pad = round_up(d->Cout, YOLO_COUT_PAD);
-    a.nchunks = (cin_p * es + 63) / 64 * dtype_kpasses(d->dtype);
-    a.out_f32 = d->out_f32;
-    a.d2s = 0;
-    a.halo_strict = 0;
-    a.up2 = d->upsample2x ? 1 : 0;
-    // (the bound is on BYTES: the kernels hold the pixel pitch x_ps * sizeof(T) as an int)
-    if (d->x_pixel_stride < 0 || (d->x_pixel_stride && d->x_pixel_stride < (long long)cin_p * planes) || d->x_pixel_stride > 0x7fffffffLL / es) return YOLO_EINVAL;
-    a.x_ps = d->x_pixel_stride ? (int)d->x_pixel_stride : cin_p * planes;
-    a.x3_n = 0; a.x3_adj1 = 0; a.x3_adj2 = 0; a.y_lo = 0; a.r_lo = 0;
-    if (split) {
-        const long long xlo = d->x_lo_offset ? d->x_lo_offset : cin_p;
-        const long long ylo = d->y_lo_offset ? d->y_lo_offset : cout_p;
-        if (xlo < cin_p || xlo + d->Cin > a.x_ps || (xlo * es) % 16 || xlo * es > 0x3fffffffLL) return YOLO_EINVAL;      // (the plane offsets are 32-bit byte adjustments in the kernels)
-        if (!d->out_f32 && (ylo < d->Cout || (ylo * es) % 16)) return YOLO_EINVAL;      // (fp32 logits are not split: y_lo unused)
-        a.x3_n = cin_p * es / 64;
-        a.x3_adj1 = (int)(xlo * es) - a.x3_n * 64;
-        a.x3_adj2 = -a.x3_n * 64 - (int)(xlo * es);
-        a.y_lo = ylo; a.r_lo = cout_p;
-    }
-    if ((a.x_ps * es) % 16) return YOLO_EUNSUPPORTED;                 // 16-byte aligned pixel rows
-    a.slope = d->slope;
-    const int oplanes = d->out_f32 ? 1 : planes;                          // (fp32 logits are not split)
-    a.y_ps = d->y_pixel_stride ? d->y_pixel_stride : cout_p * oplanes;
-    if (split && !d->out_f32 && a.y_lo + d->Cout > a.y_ps) return YOLO_EINVAL;
-    a.y_bs = d->y_batch_stride ? d->y_batch_stride : (long long)a.Ho * a.Wo * a.y_ps * (a.up2 ? 4 : 1);
-    a.r_ps = cout_p * planes; a.r_bs = (long long)a.Ho * a.Wo * a.r_ps;  // the residual is dense
-    if (a.res && d->out_f32) return YOLO_EUNSUPPORTED;
-    if (a.up2 && (a.res || d->out_f32)) return YOLO_EUNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    if (d->algo < 0) return YOLO_EINVAL;
-    a.stats = (float*)d->stats; a.stats_mode = d->stats_mode;
-    a.s_y = (const char*)d->stats_y; a.s_mean = d->stats_mean; a.s_invstd = d->stats_invstd;
-    a.s_gamma = d->stats_gamma; a.s_beta = d->stats_beta; a.s_slope = d->stats_slope;
-    a.t_wp = (const char*)d->tail_w_packed; a.t_scale = d->tail_scale; a.t_bias = d->tail_bias; a.t_y = (char*)d->tail_y;
-    a.t_cout = d->tail_cout; a.t_out_f32 = d->tail_out_f32; a.t_slope = d->tail_slope;
-    a.t_y_ps = d->tail_y_pixel_stride ? d->tail_y_pixel_stride : d->tail_cout;
-    a.t_y_bs = d->tail_y_batch_stride ? d->tail_y_batch_stride : (long long)a.Ho * a.Wo * a.t_y_ps;
-    {
-        // extents in bytes of everything the epilogue addresses (conv_epilogue.h buf32)
-        const long long lim = 0x7fffffffLL;
-        const long long yb = (long long)a.N * a.y_bs * (a.out_f32 ? 4 : es);
-        const long long rbytes = a.res ? (long long)a.N * a.r_bs * es : 0;
-        const long long tb = a.t_wp ? (long long)a.N * a.t_y_bs * (a.t_out_f32 ? 4 : es) : 0;
-        a.buf32 = (yb < lim && rbytes < lim && tb < lim) ? conv_buf32_form() : 0;
-    }
-    { static const int lab = (int)YOLO_LAB_ENV("YOLO_EPI_AB", 0); a.lab = lab; }
-    if (d->algo == 43) return conv_flat_dispatch(a, d->ksize, d->stride, d->dtype, st, nm);      // (refuses a tail, statistics, strided views itself)
-    if (a.t_wp) {
-        // fused tail 1x1: pipelined 3x3 variants with 256-cout tiles only (conv_pipe.hip)
-        if (!d->tail_y || (!d->tail_scale != !d->tail_bias) || d->tail_cout <= 0 || !(d->tail_slope >= 0.f && d->tail_slope <= 1.f)) return YOLO_EINVAL;
-        if (a.stats || elem_size(d->dtype) != 2 || d->ksize != 3) return YOLO_EUNSUPPORTED;
-        if (!d->tail_out_f32 && (d->tail_cout % 4)) return YOLO_EUNSUPPORTED;
-        if (d->algo) return conv_pipe_dispatch(a, d->ksize, d->stride, d->dtype, d->algo, st, nm);
-        // (tiles that hold every channel of a pixel: 128-cout tiles first when Cout <= 128, else the 256-cout ones)
-        static const int s1a[] = {7, 6, 2}, s2a[] = {17, 9, 18, 16, 10}, s1b[] = {6, 2, 0}, s2b[] = {18, 16, 10, 0, 0};
-        const bool small = d->Cout <= 128;
-        const int* cand = d->stride == 2 ? (small ? s2a : s2b) : (small ? s1a : s1b);
-        const int ncand = d->stride == 2 ? (small ? 5 : 3) : (small ? 3 : 2);
-        for (int k = 0; k < ncand; ++k) {
-            ConvArgs b = a;
-            const int rc = conv_pipe_dispatch(b, d->ksize, d->stride, d->dtype, cand[k], st, nm);
-            if (rc != YOLO_EUNSUPPORTED) return rc;
-        }
-        return YOLO_EUNSUPPORTED;
-    }
-    if (a.stats) {
-        // BatchNorm statistics in the epilogue: the pipelined kernels only (yolo_conv_stats_rows tells the caller beforehand)
-        if (a.stats_mode != 1 && a.stats_mode != 2) return YOLO_EINVAL;
-        if (a.stats_mode == 2 && (!a.s_y || !a.s_mean || !a.s_invstd || !a.s_gamma || !a.s_beta)) return YOLO_EINVAL;
-        int algo = d->algo;
-        if (algo == 13 || algo == 14) return conv_stream_dispatch(a, d->ksize, d->stride, d->dtype, algo, st, nm);
-        if (algo == 0) {
-            if (d->ksize == 3 && d->Cin <= 64 && !(d->stride == 2 && d->Cin == 64)) {          // (as in the plain path below)
-                const int rc = conv_stream_dispatch(a, d->ksize, d->stride, d->dtype, 13, st, nm);
-                if (rc != YOLO_EUNSUPPORTED) return rc;
-            }
-            algo = conv_auto_algo(a, d->ksize, d->stride, d->dtype);
-        }
-        if (algo >= 2) {
-            ConvArgs b = a;
-            int rc = conv_pipe_dispatch(b, d->ksize, d->stride, d->dtype, algo, st, nm);
-            if (rc == YOLO_EUNSUPPORTED && !d->algo && algo >= 27) {       // (halo of the pixel-heavy tile does not fit: the next best)
-                b = a;
-                rc = conv_pipe_dispatch(b, d->ksize, d->stride, d->dtype, conv_auto_algo(a, d->ksize, d->stride, d->dtype, false), st, nm);
-            }
-            if (rc != YOLO_EUNSUPPORTED || d->algo) return rc;
-        }
-        if (a.stats_mode != 1 || d->dtype != YOLO_BF16) return YOLO_EUNSUPPORTED;   // generic kernel: forward sums, bf16
-        return launch_dtype<bf16_t>(a, d->ksize, d->stride, st, nm);
-    }
-    if (d->algo == 13 || d->algo == 14) return conv_stream_dispatch(a, d->ksize, d->stride, d->dtype, d->algo, st, nm);
-    if (d->algo >= 30 && d->algo <= 35) return conv_sk_dispatch(a, d->ksize, d->stride, d->dtype, d->algo, st, nm);
-    if (d->algo >= 2) return conv_pipe_dispatch(a, d->ksize, d->stride, d->dtype, d->algo, st, nm);
-    if (d->algo == 0) {
-        // small-channel 3x3 layers: the streaming kernel (measured 1.2-1.45x the generic one; the 1x1s and the
-        // 64->128 stride-2 layer are a wash and stay where they were)
-        if (!split && d->ksize == 3 && d->Cin <= 64 && !(d->stride == 2 && d->Cin == 64)) {
-            const int rc = conv_stream_dispatch(a, d->ksize, d->stride, d->dtype, 13, st, nm);
-            if (rc != YOLO_EUNSUPPORTED) return rc;
-        }
-        const int pick = conv_auto_algo(a, d->ksize, d->stride, d->dtype);
-        if (pick >= 2) {
-            ConvArgs b = a;
-            int rc = conv_pipe_dispatch(b, d->ksize, d->stride, d->dtype, pick, st, nm);
-            if (rc == YOLO_EUNSUPPORTED && pick == 18) {
-                b = a;
-                rc = conv_pipe_dispatch(b, d->ksize, d->stride, d->dtype, 10, st, nm);
-            }
-            if (rc == YOLO_EUNSUPPORTED && pick >= 27) {       // (the halo of a 384 / 512-pixel tile does not fit every map: the next best)
-                b = a;
-                rc = conv_pipe_dispatch(b, d->ksize, d->stride, d->dtype, conv_auto_algo(a, d->ksize, d->stride, d->dtype, false), st, nm);
-            }
-            if (rc != YOLO_EUNSUPPORTED) return rc;
-        }
-    }
-    if (d->dtype == YOLO_BF16) return launch_dtype<bf16_t>(a, d->ksize, d->stride, st, nm);
-    if (d->dtype == YOLO_F16) return launch_dtype<f16_t>(a, d->ksize, d->stride, st, nm);
-    if (d->dtype == YOLO_BF16X3) return launch_dtype<bf16x3_t>(a, d->ksize, d->stride, st, nm);      // (ragged widths, maps a pixel or two wide: the generic kernel)
-    if (d->dtype == YOLO_F16X3) return launch_dtype<f16x3_t>(a, d->ksize, d->stride, st, nm);
-    return launch_dtype<float>(a, d->ksize, d->stride, st, nm);
-}
-
-// Data gradient of a 3x3 stride-2 pad-1 convolution without the zero-dilated dy: the four sub-pixel phases of dx are
-// four output-channel blocks of ONE 2x2-window convolution over dy (16 instead of 36 tap-products per dy pixel) whose
-// epilogue stores depth-to-space.  Even H/W of dx only (2H x 2W); bf16; pipelined variants only -- callers fall back
-// to yolo_dilate2x + yolo_conv_fwd on YOLO_EUNSUPPORTED.
-extern "C" int yolo_conv_dgrad_s2(const yolo_conv_desc* d, void* stream) {
-    if (!d || !d->x || !d->w_packed || !d->y || (!d->scale != !d->bias)) return YOLO_EINVAL;      // (both NULL: identity epilogue)
-    if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->algo < 0) return YOLO_EINVAL;
-    if (!(d->slope >= 0.f && d->slope <= 1.f)) return YOLO_EINVAL;
-    if (d->dtype != YOLO_BF16 || d->out_f32 || d->y_pixel_stride || d->y_batch_stride) return YOLO_EUNSUPPORTED;
-    if ((d->Cout % 32) || (d->Cin * 2) % 64) return YOLO_EUNSUPPORTED;      // a lane's 8 couts stay inside one phase
-    ConvArgs a;
-    a.x = (const char*)d->x; a.wp = (const char*)d->w_packed; a.scale = d->scale; a.bias = d->bias;
-    a.res = (const char*)d->residual; a.y = (char*)d->y;
-    a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout;
-    a.Ho = d->H; a.Wo = d->W;
-    a.Cout_pad = round_up(d->Cout, YOLO_COUT_PAD);
-    a.nchunks = (d->Cin * 2 + 63) / 64;
-    a.out_f32 = 0; a.d2s = 1; a.up2 = 0; a.x_ps = d->Cin; a.slope = d->slope;
-    a.halo_strict = 0;
-    a.stats = nullptr; a.stats_mode = 0;
-    a.t_wp = nullptr;
-    a.x3_n = 0; a.x3_adj1 = 0; a.x3_adj2 = 0; a.y_lo = 0; a.r_lo = 0;
-    a.lab = 0;
-    a.buf32 = ((long long)a.N * a.Ho * a.Wo * d->Cout * 2 < 0x7fffffffLL) ? conv_buf32_form() : 0;      // (dx: N x 2Ho x 2Wo x Cout/4, residual = dx)
-    if (d->x_pixel_stride || d->upsample2x || d->stats) return YOLO_EUNSUPPORTED;
-    a.y_ps = d->Cout / 4;
-    a.y_bs = (long long)a.Ho * a.Wo * d->Cout;
-    a.r_ps = a.y_ps; a.r_bs = a.y_bs;                    // (accumulation into dx: same depth-to-space addressing)
-    hipStream_t st = (hipStream_t)stream;
-    if (d->algo) return conv_pipe_dispatch(a, 2, 1, d->dtype, d->algo, st, nullptr);
-    // rounds x tile cost as in conv_auto_algo, then the first variant whose halo fits
-    struct V { int algo, bp, bc, bpc; };
-    static const V vs[] = {{2, 256, 256, 1}, {6, 192, 256, 1}, {10, 128, 256, 1}, {4, 128, 128, 2}};      // (algo 4: large regular maps only, conv_pipe.hip)
-    const long long px = (long long)a.N * a.Ho * a.Wo;
-    double cost[4];
-    for (int i = 0; i < 4; ++i) {
-        const long long tiles = ((px + vs[i].bp - 1) / vs[i].bp) * ((a.Cout + vs[i].bc - 1) / vs[i].bc);
-        const long long slots = 256LL * vs[i].bpc;
-        cost[i] = (double)((tiles + slots - 1) / slots) * vs[i].bp * vs[i].bc * vs[i].bpc;
-    }
-    bool used[4] = {false, false, false, false};
-    for (int k = 0; k < 4; ++k) {
-        int b = -1;
-        for (int i = 0; i < 4; ++i)
-            if (!used[i] && (b < 0 || cost[i] < cost[b])) b = i;
-        used[b] = true;
-        ConvArgs t = a;
-        const int rc = conv_pipe_dispatch(t, 2, 1, d->dtype, vs[b].algo, st, nullptr);
-        if (rc != YOLO_EUNSUPPORTED) return rc;
-    }
-    return YOLO_EUNSUPPORTED;
+// The generic kernel for every element type (algo 1, and the last candidate of the automatic choice: conv_dispatch.hip).
+int conv_igemm_dispatch(ConvArgs& a, int ks, int stride, int dtype, hipStream_t st, const NameOut* nm) {
+    if (a.t_wp) return YOLO_EUNSUPPORTED;      // (a fused tail: conv_pipe.hip only)
+    if (dtype == YOLO_BF16) return launch_dtype<bf16_t>(a, ks, stride, st, nm);
+    if (dtype == YOLO_F16) return launch_dtype<f16_t>(a, ks, stride, st, nm);
+    if (dtype == YOLO_BF16X3) return launch_dtype<bf16x3_t>(a, ks, stride, st, nm);      // (ragged widths, maps a pixel or two wide: the generic kernel)
+    if (dtype == YOLO_F16X3) return launch_dtype<f16x3_t>(a, ks, stride, st, nm);
+    return launch_dtype<float>(a, ks, stride, st, nm);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -26,17 +26,19 @@
 #include <type_traits>
 #include <atomic>
 
-// The file is compiled FOUR times (csrc/Makefile), kernel kind x element type, so that the ~270 instantiations build in parallel:
-//   YOLO_PIPE_PART 0: 3x3 kernels, bf16 + conv_pipe_dispatch     1: 2x2-window and 1x1 kernels, bf16 (conv_pipe_dispatch_b)
-//                  2: 3x3 kernels, f16 and f32 (.._dispatch_c)   3: 1x1 kernels, f16 and f32 (conv_pipe_dispatch_d)
-//                  4: 3x3 stride-2 kernels, bf16 (conv_pipe_dispatch_e)
-//                  5: 3x3 stride-1 kernels, bf16, the second half of the tile variants (conv_pipe_dispatch_f)
-//                  6: 3x3 kernels, split bf16 (YOLO_BF16X3; conv_pipe_dispatch_g)      7: 1x1 kernels, split bf16 (conv_pipe_dispatch_h)
-//                  8 / 9: the same for split f16 (YOLO_F16X3; conv_pipe_dispatch_i / _j)
-#define YOLO_PIPE_3X3 (YOLO_PIPE_PART == 0 || YOLO_PIPE_PART == 2 || YOLO_PIPE_PART == 4 || YOLO_PIPE_PART == 5 || YOLO_PIPE_PART == 6 || YOLO_PIPE_PART == 8)
-// (which stride-1 3x3 variants a unit holds: bf16 is split over units 0 and 5)
+// The file is compiled TEN times (csrc/Makefile), kernel kind x element type, so that the ~390 instantiations build in parallel.
+// Part n exports conv_pipe_part<n> (one signature, at the end of the file); part 0 also holds conv_pipe_dispatch, which picks the
+// part that owns (dtype, ks, stride, id) -- pipe_owner -- and calls it.  No part calls another.
+//   YOLO_PIPE_PART 0: bf16, 3x3 stride 1, ids 2 3 4 6 7 8        5: bf16, 3x3 stride 1, every other id
+//                  4: bf16, 3x3 stride 2                         1: bf16, 1x1 and the 2x2 window
+//                  2: f16 and f32, 3x3 (both strides)            3: f16 and f32, 1x1
+//                  6: split bf16 (YOLO_BF16X3), 3x3              7: split bf16, 1x1
+//                  8: split f16 (YOLO_F16X3), 3x3                9: split f16, 1x1
+// which kernels a part holds: 3x3 stride 2, the two halves of the 3x3 stride-1 ids, 1x1 with the 2x2 window
+#define YOLO_PIPE_S2 (YOLO_PIPE_PART == 2 || YOLO_PIPE_PART == 4 || YOLO_PIPE_PART == 6 || YOLO_PIPE_PART == 8)
 #define YOLO_PIPE_S1A (YOLO_PIPE_PART == 0 || YOLO_PIPE_PART == 2 || YOLO_PIPE_PART == 6 || YOLO_PIPE_PART == 8)
 #define YOLO_PIPE_S1B (YOLO_PIPE_PART == 5 || YOLO_PIPE_PART == 2 || YOLO_PIPE_PART == 6 || YOLO_PIPE_PART == 8)
+#define YOLO_PIPE_1X1 (YOLO_PIPE_PART == 1 || YOLO_PIPE_PART == 3 || YOLO_PIPE_PART == 7 || YOLO_PIPE_PART == 9)
 namespace { __device__ __attribute__((aligned(64))) unsigned int yolo_zero_page[16]; }
 
 typedef __attribute__((address_space(3))) char lds_char;
@@ -867,38 +869,22 @@ static int launch_pipe(ConvArgs& a, hipStream_t st, const NameOut* name) {
 #undef YOLO_PIPE_LAUNCH
 }
 
-// algo ids (yolo_conv_desc.algo): 1 = generic (conv_igemm.hip); pipelined variants:
-//   2: 8 waves, 256 px x 256 cout (wave tile 128x64)   3: 8 waves, 256 px x 128 cout (wave tile 64x64)
-//   4: 4 waves, 128 px x 128 cout (wave tile 64x64)    5: 8 waves, 128 px x 256 cout (wave tile 128x32)
-//   6: 8 waves, 192 px x 256 cout (wave tile 96x64)    7: 8 waves, 192 px x 128 cout (wave tile 96x32)
-//   8: 4 waves, 192 px x 128 cout (wave tile 96x64)    -- 192-pixel tiles exist to cut tile quantisation
-//   9 / 10: 3x3 stride 2, 8 waves, 128 px x 128 / 256 cout; 17 / 16: the same with a smaller halo buffer and a
-//           4-slot weight ring
-//   11: 4 waves, 64 px x 128 cout; 12 (1x1 only): 4 waves, 64 px x 256 cout -- small-M layers (13x13 maps at
-//       batch 32 have 5408 pixels: more, smaller tiles fill the chip)
-//   26: 3x3 stride 1, bf16: 4 waves, 256 px x 256 cout, wave tile 128x128 -- ONE wave per SIMD (256 accumulator registers),
-//       a third fewer LDS fragment reads per MFMA than algo 2, fragments double-buffered in registers (the W1 loop).
+// Which unit owns which id: conv_dispatch.hip.  A tile's shape is what its case label below instantiates (BP = WAVES_P * NI * 32
+// pixels x BC = WAVES_C * MI * 32 couts).  Why some of them exist:
+//   192-pixel tiles (6 7 8) cut tile quantisation; 11 / 12: small-M layers (13x13 maps at batch 32 have 5408 pixels: more, smaller
+//       tiles fill the chip)
+//   26: ONE wave per SIMD (256 accumulator registers), a third fewer LDS fragment reads per MFMA than algo 2, fragments
+//       double-buffered in registers (the W1 loop).
 //       Measured at batch 64: 1328 vs 1311 TFLOP/s on 19x19 1024->2048, 1263 vs 1276 on 38x38 512->1024, 1120 vs 1172 on
 //       76x76 256->512; a 192 px x 256 cout sibling (wave tile 128x96) ties algo 6 at batch 32 (1167 vs 1168, 1100 vs 1125)
 //       and was removed: the long-K layers are not bound by LDS traffic or by the loop structure (power / clock)
 //   (also tried: algo 4 with a 2-slot weight ring = 48 KB of LDS, three blocks per CU -- 4-10 % faster than algo 4 on the short-K
 //    layers, never faster than the 192-pixel tiles there, which fit neither three blocks of LDS nor of registers; removed)
-int conv_pipe_dispatch_b(ConvArgs& a, int ks, int dtype, int algo, hipStream_t st, const NameOut* nm);                 // (unit 1)
-int conv_pipe_dispatch_c(ConvArgs& a, int ks, int stride, int dtype, int algo, hipStream_t st, const NameOut* nm);     // (unit 2)
-int conv_pipe_dispatch_d(ConvArgs& a, int ks, int dtype, int algo, hipStream_t st, const NameOut* nm);                 // (unit 3)
-int conv_pipe_dispatch_e(ConvArgs& a, int algo, hipStream_t st, const NameOut* nm);                                    // (unit 4)
-int conv_pipe_dispatch_f(ConvArgs& a, int algo, hipStream_t st, const NameOut* nm);                                    // (unit 5)
-int conv_pipe_dispatch_g(ConvArgs& a, int ks, int stride, int algo, hipStream_t st, const NameOut* nm);                // (unit 6)
-int conv_pipe_dispatch_h(ConvArgs& a, int ks, int algo, hipStream_t st, const NameOut* nm);                            // (unit 7)
-int conv_pipe_dispatch_i(ConvArgs& a, int ks, int stride, int algo, hipStream_t st, const NameOut* nm);                // (unit 8)
-int conv_pipe_dispatch_j(ConvArgs& a, int ks, int algo, hipStream_t st, const NameOut* nm);                            // (unit 9)
 
+// The kernels of THIS part for element type T; YOLO_EUNSUPPORTED for an id (or a window) the part does not hold.
 template <typename T>
-static int pipe_dispatch_t(ConvArgs& a, int ks, int stride, int algo, hipStream_t st, const NameOut* nm) {
-#if YOLO_PIPE_PART == 0
-    if (ks == 3 && stride == 2) return conv_pipe_dispatch_e(a, algo, st, nm);      // (bf16: a unit of its own)
-#endif
-#if YOLO_PIPE_PART == 2 || YOLO_PIPE_PART == 4 || YOLO_PIPE_PART == 6 || YOLO_PIPE_PART == 8
+static int pipe_part_t(ConvArgs& a, int ks, int stride, int algo, hipStream_t st, const NameOut* nm) {
+#if YOLO_PIPE_S2
     if (ks == 3 && stride == 2) {
         // stride 2: the input footprint is ~4x the output tile, so tiles are 128 output pixels
         switch (algo) {
@@ -916,10 +902,8 @@ static int pipe_dispatch_t(ConvArgs& a, int ks, int stride, int algo, hipStream_
         return YOLO_EUNSUPPORTED;
     }
 #endif
-#if YOLO_PIPE_PART == 4
-    return YOLO_EUNSUPPORTED;
-#elif YOLO_PIPE_3X3
-    if (ks == 3) {
+#if YOLO_PIPE_S1A || YOLO_PIPE_S1B
+    if (ks == 3 && stride == 1) {
         switch (algo) {
 #if YOLO_PIPE_S1A
             case 2: return launch_pipe<T, 3, 2, 4, 2, 4, 512>(a, st, nm);
@@ -928,9 +912,6 @@ static int pipe_dispatch_t(ConvArgs& a, int ks, int stride, int algo, hipStream_
             case 6: return launch_pipe<T, 3, 2, 4, 2, 3, 384>(a, st, nm);
             case 7: return launch_pipe<T, 3, 2, 4, 1, 3, 384>(a, st, nm);
             case 8: return launch_pipe<T, 3, 2, 2, 2, 3, 384>(a, st, nm);      // (384 slots = 80 KB with the 4-slot ring: still two blocks per CU; room for the padded pitch on 13-wide strips)
-#endif
-#if YOLO_PIPE_PART == 0
-            default: return conv_pipe_dispatch_f(a, algo, st, nm);
 #endif
 #if YOLO_PIPE_S1B
             case 5: return launch_pipe<T, 3, 1, 8, 1, 4, 256>(a, st, nm);
@@ -952,18 +933,8 @@ static int pipe_dispatch_t(ConvArgs& a, int ks, int stride, int algo, hipStream_
         }
         return YOLO_EUNSUPPORTED;
     }
-#if YOLO_PIPE_PART == 5
-    return YOLO_EUNSUPPORTED;
-#elif YOLO_PIPE_PART == 0
-    return conv_pipe_dispatch_b(a, ks, Elem<T>::dtype, algo, st, nm);
-#elif YOLO_PIPE_PART == 6
-    return conv_pipe_dispatch_h(a, ks, algo, st, nm);
-#elif YOLO_PIPE_PART == 8
-    return conv_pipe_dispatch_j(a, ks, algo, st, nm);
-#else
-    return conv_pipe_dispatch_d(a, ks, Elem<T>::dtype, algo, st, nm);
 #endif
-#else
+#if YOLO_PIPE_1X1
     if (ks == 2) {
         // 2x2 window (yolo_conv_dgrad_s2, bf16 only): four phases per K chunk
         if constexpr (IsBf16<T>::value) {
@@ -977,7 +948,7 @@ static int pipe_dispatch_t(ConvArgs& a, int ks, int stride, int algo, hipStream_
         }
         return YOLO_EUNSUPPORTED;
     }
-    {
+    if (ks == 1) {
         switch (algo) {
             // 1x1: the lean K loop wherever the K extent allows it (>= 4 phases), the generic loop otherwise
 #define YOLO_PIPE1(...)                                                                        \
@@ -1019,46 +990,49 @@ static int pipe_dispatch_t(ConvArgs& a, int ks, int stride, int algo, hipStream_
             case 25: return launch_pipe<T, 1, 1, 4, 2, 2, 64, 1, 0, 2, 1>(a, st, nm);   // 64 px x 256 cout
         }
     }
+#endif
     return YOLO_EUNSUPPORTED;
+}
+
+// Every part's entry: conv_pipe_part<YOLO_PIPE_PART>, conv_pipe_dispatch's parameter list.
+#define YOLO_PIPE_ENTRY_(n) conv_pipe_part##n
+#define YOLO_PIPE_ENTRY(n) YOLO_PIPE_ENTRY_(n)
+typedef int PipePartFn(ConvArgs& a, int ks, int stride, int dtype, int algo, hipStream_t st, const NameOut* nm);
+PipePartFn conv_pipe_part0, conv_pipe_part1, conv_pipe_part2, conv_pipe_part3, conv_pipe_part4, conv_pipe_part5, conv_pipe_part6,
+    conv_pipe_part7, conv_pipe_part8, conv_pipe_part9;
+
+int YOLO_PIPE_ENTRY(YOLO_PIPE_PART)(ConvArgs& a, int ks, int stride, int dtype, int algo, hipStream_t st, const NameOut* nm) {
+#if YOLO_PIPE_PART == 2 || YOLO_PIPE_PART == 3
+    if (dtype == YOLO_F16) return pipe_part_t<f16_t>(a, ks, stride, algo, st, nm);
+    return pipe_part_t<float>(a, ks, stride, algo, st, nm);
+#elif YOLO_PIPE_PART == 6 || YOLO_PIPE_PART == 7
+    return pipe_part_t<bf16x3_t>(a, ks, stride, algo, st, nm);
+#elif YOLO_PIPE_PART == 8 || YOLO_PIPE_PART == 9
+    return pipe_part_t<f16x3_t>(a, ks, stride, algo, st, nm);
+#else
+    return pipe_part_t<bf16_t>(a, ks, stride, algo, st, nm);
 #endif
 }
 
-#if YOLO_PIPE_PART == 5
-int conv_pipe_dispatch_f(ConvArgs& a, int algo, hipStream_t st, const NameOut* nm) { return pipe_dispatch_t<bf16_t>(a, 3, 1, algo, st, nm); }
-#elif YOLO_PIPE_PART == 4
-int conv_pipe_dispatch_e(ConvArgs& a, int algo, hipStream_t st, const NameOut* nm) { return pipe_dispatch_t<bf16_t>(a, 3, 2, algo, st, nm); }
-#elif YOLO_PIPE_PART == 1
-int conv_pipe_dispatch_b(ConvArgs& a, int ks, int dtype, int algo, hipStream_t st, const NameOut* nm) {
-    return pipe_dispatch_t<bf16_t>(a, ks, 1, algo, st, nm);
+#if YOLO_PIPE_PART == 0
+// The part that holds the kernels of (dtype, ks, stride, id): the table at the top of the file.
+static PipePartFn* pipe_owner(int dtype, int ks, int stride, int algo) {
+    const bool k3 = ks == 3;
+    if (dtype == YOLO_BF16X3) return k3 ? conv_pipe_part6 : conv_pipe_part7;
+    if (dtype == YOLO_F16X3) return k3 ? conv_pipe_part8 : conv_pipe_part9;
+    if (dtype != YOLO_BF16) return k3 ? conv_pipe_part2 : conv_pipe_part3;        // (f16, f32)
+    if (!k3) return conv_pipe_part1;
+    if (stride == 2) return conv_pipe_part4;
+    const bool first_half = algo == 2 || algo == 3 || algo == 4 || algo == 6 || algo == 7 || algo == 8;
+    return first_half ? conv_pipe_part0 : conv_pipe_part5;
 }
-#elif YOLO_PIPE_PART == 3
-int conv_pipe_dispatch_d(ConvArgs& a, int ks, int dtype, int algo, hipStream_t st, const NameOut* nm) {
-    if (dtype == YOLO_F16) return pipe_dispatch_t<f16_t>(a, ks, 1, algo, st, nm);
-    return pipe_dispatch_t<float>(a, ks, 1, algo, st, nm);
-}
-#elif YOLO_PIPE_PART == 6
-int conv_pipe_dispatch_g(ConvArgs& a, int ks, int stride, int algo, hipStream_t st, const NameOut* nm) { return pipe_dispatch_t<bf16x3_t>(a, ks, stride, algo, st, nm); }
-#elif YOLO_PIPE_PART == 7
-int conv_pipe_dispatch_h(ConvArgs& a, int ks, int algo, hipStream_t st, const NameOut* nm) { return pipe_dispatch_t<bf16x3_t>(a, ks, 1, algo, st, nm); }
-#elif YOLO_PIPE_PART == 8
-int conv_pipe_dispatch_i(ConvArgs& a, int ks, int stride, int algo, hipStream_t st, const NameOut* nm) { return pipe_dispatch_t<f16x3_t>(a, ks, stride, algo, st, nm); }
-#elif YOLO_PIPE_PART == 9
-int conv_pipe_dispatch_j(ConvArgs& a, int ks, int algo, hipStream_t st, const NameOut* nm) { return pipe_dispatch_t<f16x3_t>(a, ks, 1, algo, st, nm); }
-#elif YOLO_PIPE_PART == 2
-int conv_pipe_dispatch_c(ConvArgs& a, int ks, int stride, int dtype, int algo, hipStream_t st, const NameOut* nm) {
-    if (dtype == YOLO_F16) return pipe_dispatch_t<f16_t>(a, ks, stride, algo, st, nm);
-    return pipe_dispatch_t<float>(a, ks, stride, algo, st, nm);
-}
-#else
+
 int conv_pipe_dispatch(ConvArgs& a, int ks, int stride, int dtype, int algo, hipStream_t st, const NameOut* nm) {
     if ((ks != 1 && ks != 2 && ks != 3) || (stride != 1 && !(ks == 3 && stride == 2))) return YOLO_EUNSUPPORTED;
     if (a.d2s && ks != 2) return YOLO_EUNSUPPORTED;
     if (!dtype_split(dtype) && (a.Cin * elem_size(dtype)) % 64) return YOLO_EUNSUPPORTED;      // (split planes are padded to whole chunks by the caller)
     if (ks == 1 && a.nchunks < 2) return YOLO_EUNSUPPORTED;     // a 1x1 needs >= 2 phases; a 3x3 has 9 per chunk
     if ((long long)a.N * a.H * a.W * a.x_ps * elem_size(dtype) >= 0xffffff00LL) return YOLO_EUNSUPPORTED;
-    if (dtype == YOLO_BF16) return pipe_dispatch_t<bf16_t>(a, ks, stride, algo, st, nm);
-    if (dtype == YOLO_BF16X3) return ks == 2 ? YOLO_EUNSUPPORTED : conv_pipe_dispatch_g(a, ks, stride, algo, st, nm);
-    if (dtype == YOLO_F16X3) return ks == 2 ? YOLO_EUNSUPPORTED : conv_pipe_dispatch_i(a, ks, stride, algo, st, nm);
-    return conv_pipe_dispatch_c(a, ks, stride, dtype, algo, st, nm);
+    return pipe_owner(dtype, ks, stride, algo)(a, ks, stride, dtype, algo, st, nm);      // (the 2x2 window exists for bf16 only: every other part refuses it)
 }
 #endif
