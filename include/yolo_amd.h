@@ -41,10 +41,14 @@ extern "C" {
  * lo = bf16_rne(v - hi).  Everything else returns YOLO_EUNSUPPORTED / YOLO_EINVAL for it (the _partials entries,
  * yolo_conv_dgrad_s2, yolo_pack_batch_blocks, yolo_conv_wgrad / _algo and yolo_add among them). */
 #define YOLO_BF16X3 3
-/* The same scheme on IEEE-half pairs (22 significant bits; the dropped term is 2^-22 of a product): decoded boxes indistinguishable from
- * the fp32 path's (6e-5 on the D53 random-BN nets, where YOLO_BF16X3 measures 3e-4) at the same three MFMAs per product -- for data inside
- * half's range (|v| < 65504; the lo planes live in the subnormals, which v_mfma_f32_32x32x16_f16 honours: tools/probes/f16_denorm_probe.py).
- * Same entry points, layout and restrictions as YOLO_BF16X3. */
+/* The same scheme on IEEE-half pairs: decoded boxes indistinguishable from the fp32 path's (6e-5 on the D53 random-BN nets, where
+ * YOLO_BF16X3 measures 3e-4) at the same three MFMAs per product.  Precision: 22 significant bits (the dropped term 2^-22 of a
+ * product) ONLY while the lo plane is normal or near it -- lo lives in half's subnormals, whose spacing is 2^-24 (which
+ * v_mfma_f32_32x32x16_f16 honours: tools/probes/f16_denorm_probe.py), so below |v| ~ 2^-3 a stored value has an ABSOLUTE error floor
+ * of 2^-25 instead: 11 bits are left at |v| = 2^-14, where hi turns subnormal too (measured against float64 on a 64 -> 64 3x3:
+ * 4.6e-7 relative on O(1) operands, 2.3e-5 with x * 2^-10, 3.8e-4 with x * 2^-14; YOLO_BF16X3: 7.0e-6 at every scale).  Range:
+ * |v| <= 65504; beyond it hi is Inf and lo = v - hi is Inf or NaN, and an Inf even in a channel that only meets zero weights turns the
+ * sums into NaN.  Nothing checks either limit.  Same entry points, layout and restrictions as YOLO_BF16X3. */
 #define YOLO_F16X3 4
 
 #define YOLO_OK 0
@@ -133,7 +137,8 @@ typedef struct yolo_conv_desc {
                               43: csrc/conv_flat.hip), YOLO_EUNSUPPORTED if not eligible              */
     long long x_pixel_stride; /* elements between pixels in x; 0 = dense Cin.  > Cin: x is a channel slice of a wider
                               NHWC buffer (the route half of a concat buffer, car/utils.py:93); images stay
-                              H*W*x_pixel_stride apart.  The pitch in BYTES must stay below 2^31
+                              H*W*x_pixel_stride apart.  Split types: see x_lo_offset for what a slice with
+                              Cin % 32 != 0 needs behind it.  The pitch in BYTES must stay below 2^31
                               (YOLO_EINVAL); pinned tile variants also refuse an x of 0xffffff00 bytes or more
                               (YOLO_EUNSUPPORTED; algo 0 runs the generic kernel then)        */
     int upsample2x;        /* 1: every output pixel is stored to the 2x2 patch (2oy..2oy+1, 2ox..2ox+1) of a
@@ -176,7 +181,14 @@ typedef struct yolo_conv_desc {
     /* split types only (YOLO_BF16X3 / YOLO_F16X3; ignored otherwise): elements between a pixel's hi plane and its lo plane in x and in y; 0 = dense
      * (round_up(Cin, 32), round_up(Cout, 32)).  A channel slice of a wider split buffer of Ctot channels (the halves of a concat
      * buffer, car/utils.py:93) has pixel stride 2 * Ctot and lo offset Ctot.  Dense strides of a split tensor count both padded
-     * planes (pixel stride 2 * round_up(C, 32)); the residual is dense; y_lo_offset is not used when out_f32. */
+     * planes (pixel stride 2 * round_up(C, 32)); the residual is dense; y_lo_offset is not used when out_f32.
+     * THE KERNELS READ x IN WHOLE 32-CHANNEL K-CHUNKS, whatever Cin is: round_up(Cin, 32) channels from x and round_up(Cin, 32)
+     * from x + x_lo_offset.  Both runs must lie inside the pixel (inside [pixel start, pixel start + x_pixel_stride) of the buffer
+     * x was sliced from), and whatever they hold beyond the first Cin channels must be FINITE: it meets zero weights, and an Inf or
+     * NaN there turns the sums into NaN.  YOLO_EINVAL when x_lo_offset + round_up(Cin, 32) > x_pixel_stride; the library cannot
+     * see where in its buffer a slice starts, so for channels [c0, c0 + Cin) of a buffer with planes of Cp channels the caller
+     * provides Cp >= c0 + round_up(Cin, 32) (zeroed pad channels count).  Stores have no such reach: exactly channels
+     * [0, Cout) of both planes of y are written. */
     long long x_lo_offset;
     long long y_lo_offset;
 } yolo_conv_desc;

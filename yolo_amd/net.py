@@ -21,8 +21,8 @@ _LIB_DT = {'bf16': L.BF16, 'f16': L.F16, 'f32': L.F32, 'bf16x3': L.BF16X3, 'f16x
 # (include/yolo_amd.h: YOLO_BF16X3).  The path on which the north-star tolerance and the MFMA rate meet: decoded boxes within
 # 1e-3 of the fp32 oracle (~3e-4 on the random-BN D53 nets, tests/test_gpu_boxes.py) at ~1/3 of the bf16 path's speed, where
 # the exact-fp32 MFMA of dtype 'f32' runs at ~1/8.  A split activation is a (N, H, W, 2, C) bf16 tensor: plane 0 = hi, 1 = lo.
-# 'f16x3': the same with IEEE-half pairs (22 significant bits): boxes as close to the fp32 oracle as the fp32 path's own (6e-5), for nets whose
-# activations stay inside half's range (as dtype 'f16' needs); same speed minus the ~4 % half multiplies cost at the power cap.
+# 'f16x3': the same with IEEE-half pairs: boxes as close to the fp32 oracle as the fp32 path's own (6e-5); same speed minus the ~4 % half
+# multiplies cost at the power cap.  Its precision and range: the CarNet docstring (include/yolo_amd.h: YOLO_F16X3).
 _SPLIT = ('bf16x3', 'f16x3')
 
 
@@ -40,6 +40,12 @@ class _Plan(object):
 
 
 class CarNet(object):
+    """dtype: 'bf16' | 'f16' | 'f32' | 'bf16x3' | 'f16x3' -- the element type of activations and weights (include/yolo_amd.h).
+    'f16x3' (IEEE-half pairs) has 22 significant bits ONLY while the lo plane is normal or near it: lo lives in half's subnormals,
+    whose spacing is 2^-24, so below |v| ~ 2^-3 a stored value has an ABSOLUTE error floor of 2^-25 instead (11 bits are left at
+    |v| = 2^-14, where hi turns subnormal too; 'bf16x3' keeps its 16 bits at every scale).  Its range is |v| <= 65504: beyond it hi
+    is Inf and lo Inf or NaN, and an Inf even in a channel that only meets zero weights turns the sums into NaN.  Nothing checks
+    either limit: a net whose activations or weights leave them (as dtype 'f16' would overflow on) wants 'bf16x3'."""
     ALGOS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 30, 31, 32, 33, 35, 36, 37, 38, 39, 40, 41, 42, 43)     # yolo_conv_desc.algo ids tried by tune='measure' (40-42: split type only; 43: the flat streaming 1x1, lib.CONV_FLAT_ALGO)
 
     def __init__(self, spec, num_sync_bn_devices=-1, dtype='bf16', device='cuda:0', tune='auto', tune_cache=None,
@@ -215,27 +221,28 @@ class CarNet(object):
             self.prepare()
 
     # ---- plan construction --------------------------------------------------------------------------
-    def _act(self, N, H, W, Cc):
+    def _act(self, N, H, W, Cc, plane=0):
         """An activation buffer of logical shape (N, H, W, C): NHWC in the net's element type; a split type (bf16x3) carries the
-        hi and lo planes of a pixel side by side -- (N, H, W, 2, C)."""
+        hi and lo planes of a pixel side by side -- (N, H, W, 2, C).  plane: split types only -- channels a plane must hold at
+        least (a concat buffer whose route half is read in whole chunks, _build_plan)."""
         if self.dtype not in _SPLIT:
             return torch.empty((N, H, W, Cc), dtype=_TORCH_DT[self.dtype], device=self.device)
         # a split plane holds whole 32-channel K-chunks (include/yolo_amd.h): C real channels + zero pad the kernels never write
-        Cp = -(-Cc // 32) * 32
+        Cp = -(-max(Cc, plane) // 32) * 32
         if Cp == Cc:
             return torch.empty((N, H, W, 2, Cc), dtype=_TORCH_DT[self.dtype], device=self.device)
         return torch.zeros((N, H, W, 2, Cp), dtype=_TORCH_DT[self.dtype], device=self.device)[..., :Cc]
 
     def _conv_op(self, plan, c, x, xshape, residual=None, out=None, out_f32=False, y_bs=0, y_ps=0, cin=None, x_ps=0, up2=False,
-                 tail=None):
+                 tail=None, x_c0=0):
         """tail: (1x1 conv spec, its output tensor or pointer, out_f32, batch stride, pixel stride) computed by the same launch
-        (yolo_conv_desc.tail_*); the caller has checked _tail_eligible and decided (_use_tail)."""
+        (yolo_conv_desc.tail_*); the caller has checked _tail_eligible and decided (_use_tail).  x_c0: _conv_desc."""
         N, H, W, _ = xshape
         ho, wo = c.out_hw(H, W)
         if out is None:
             out = self._act(N, ho, wo, c.cout)
             plan.buffers.append(out)
-        d = self._conv_desc(c, x, xshape, out, residual, out_f32, y_bs, y_ps, cin, x_ps, up2)
+        d = self._conv_desc(c, x, xshape, out, residual, out_f32, y_bs, y_ps, cin, x_ps, up2, x_c0)
         if tail is not None:
             self._set_tail(d, *tail)
             d.algo = self._tail_algo(d)
@@ -393,7 +400,9 @@ class CarNet(object):
         """[(op, kernel instantiation)] of the launch plan for one input shape -- what must agree across ranks."""
         return [(n, k) for n, k, _ in self.plan_kernels(B, H, W)]
 
-    def _conv_desc(self, c, x, xshape, out, residual=None, out_f32=False, y_bs=0, y_ps=0, cin=None, x_ps=0, up2=False):
+    def _conv_desc(self, c, x, xshape, out, residual=None, out_f32=False, y_bs=0, y_ps=0, cin=None, x_ps=0, up2=False, x_c0=0):
+        """x_c0: the first channel of x in the buffer it is a slice of (the route half of a concat buffer: its up-sampled half's
+        width)."""
         N, H, W, _ = xshape
         wp, scale, bias = self._prepared[c.name]
         x_lo = y_lo = 0
@@ -404,6 +413,11 @@ class CarNet(object):
             x_ps = x.stride(2)
             if x.dim() == 5:
                 x_lo = x.stride(3)
+                # the split kernels read whole 32-channel chunks of both planes (include/yolo_amd.h, x_lo_offset): the lo plane's
+                # must end inside the pixel -- the library checks the same without knowing where the slice starts
+                if x_c0 + x_lo + -(-(cin or c.cin) // 32) * 32 > x_ps:
+                    raise L.YoloError('input view of %s: channels [%d, %d) of planes of %d -- the whole 32-channel chunks the split '
+                                      'kernels read would leave the pixel' % (c.name, x_c0, x_c0 + (cin or c.cin), x_lo))
         if isinstance(out, torch.Tensor) and out.dim() >= 4 and not out.is_contiguous():
             if out.stride(-1) != 1 or out.stride(1) != out.shape[2] * out.stride(2):
                 raise L.YoloError('unsupported output view for %s' % c.name)
@@ -429,7 +443,7 @@ class CarNet(object):
         lib, st = self._lib, L.stream_ptr()
         return self.tuner.conv(d, algos or self.ALGOS, lambda: lib.yolo_conv_fwd(C.byref(d), st), key_extra)
 
-    def _stage_ops(self, plan, down, res, x, shp, cat_view, down_done, tdt):
+    def _stage_ops(self, plan, down, res, x, shp, cat_view, down_done, tdt, x_c0=0):
         """The launch list of one backbone stage (down-sampling conv + residual blocks) appended to `plan`: the fused
         residual-block kernel wherever it is eligible and chosen; elsewhere a conv carries the next block's 1x1 as a fused tail
         when the pair is measured faster (_use_tail).  (Round 4 also measured, for the stage where both fusions apply -- D53's
@@ -455,7 +469,7 @@ class CarNet(object):
         if not down_done:
             dout = cat_view if not res else None
             tl, pre_mid = tail_for(down, x, shp, None, 0) if res else (None, None)
-            x, shp = self._conv_op(plan, down, x, shp, out=dout, tail=tl)
+            x, shp = self._conv_op(plan, down, x, shp, out=dout, tail=tl, x_c0=x_c0)      # (x: the route half of the last stage's concat buffer)
         for j, (c1, c2) in enumerate(res):
             last = cat_view is not None and j == len(res) - 1
             sd = plan.ops[-1] if (j == 0 and down_done and plan.ops and plan.ops[-1][0] == 'stem_down') else None
@@ -531,6 +545,7 @@ class CarNet(object):
         routes = []
         nst = len(g.stages)
         cats = {}                                            # stage index -> (concat buffer, channels of the up-sampled half)
+        x_c0 = 0                                             # x is channels [x_c0, ..) of its buffer
         for i, (down, res) in enumerate(g.stages):
             last_of_stage = res[-1][1] if res else down
             cat_view = None
@@ -539,11 +554,14 @@ class CarNet(object):
                     and last_of_stage is not fused_down and not (res and self._res_block_eligible(res[-1][0], res[-1][1]))):
                 ho, wo = down.out_hw(shp[1], shp[2])
                 up_ch = g.transitions[t_idx].cout
-                cat = self._act(B, ho, wo, up_ch + last_of_stage.cout)
+                # (split types: the next stage's down-sampling conv reads the route half in whole 32-channel chunks -- the planes
+                #  hold them, zero beyond the route: include/yolo_amd.h, x_lo_offset)
+                cat = self._act(B, ho, wo, up_ch + last_of_stage.cout, plane=up_ch + -(-last_of_stage.cout // 32) * 32)
                 plan.buffers.append(cat)
                 cats[i] = (cat, up_ch)
                 cat_view = cat[..., up_ch:]
-            x, shp = self._stage_ops(plan, down, res, x, shp, cat_view, down is fused_down, tdt)
+            x, shp = self._stage_ops(plan, down, res, x, shp, cat_view, down is fused_down, tdt, x_c0)
+            x_c0 = cats[i][1] if i in cats else 0
             if i >= nst - g.num_pyramid:
                 routes.append((x, shp, cats.get(i)))
         # merged head buffer (B, sum HW, A*C) float32, scales fine->coarse (car/utils.py:95, car/YOLO.py:841)
