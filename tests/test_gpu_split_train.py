@@ -221,6 +221,37 @@ def test_split_wgrad_batch_past_4gib(lib, cuda):
     del xs, ds
 
 
+@pytest.mark.parametrize('case', [(2, 72, 13, 13, 136, 1, 1),        # P = 338: a ragged second cout tile, a cin tail
+                                  (3, 96, 15, 17, 40, 3, 2)],        # Ho x Wo = 8 x 9, P = 216: border taps, Cout % 32 != 0
+                         ids=lambda c: 'x'.join(map(str, c)))
+def test_split_wgrad_with_zero_lo_planes_is_the_bf16_kernel_bitwise(lib, cuda, case):
+    """The split per-tap kernel is the bf16 one on (hi, lo) planes.  On operands that are exactly bf16 the lo planes are all zero,
+    so the two extra MFMAs of a fragment pair (hi x lo, lo x hi) add exact zeros, and with the same 128 x 128 tile (split algo 2;
+    the bf16 entry's algo 1 lands on the per-tap kernel: both cases are outside the strip and row-group domains) and the same
+    ascending 16-pixel K steps dw comes out bit for bit the same.  That needs one slice per launch, so that neither adds partial
+    sums atomically in an order of its own: P <= 960 keeps the bf16 launch below 16 chunks of 64 pixels and the split one below 32
+    chunks of 32."""
+    N, Cin, H, W, Cout, k, s = case
+    Ho, Wo = (H + 2 * (k // 2) - k) // s + 1, (W + 2 * (k // 2) - k) // s + 1
+    assert N * Ho * Wo <= 960
+    rng = np.random.default_rng(Cin + Cout)
+    x = torch.from_numpy(rng.standard_normal((N, H, W, Cin)).astype(np.float32)).bfloat16()
+    dy = torch.from_numpy(rng.standard_normal((N, Ho, Wo, Cout)).astype(np.float32)).bfloat16()
+    xs, dys = _to_split(x.float(), cuda), _to_split(dy.float(), cuda)
+    assert bool((xs[..., 1, :] == 0).all()) and bool((dys[..., 1, :] == 0).all()), 'lo planes of bf16 values are zero'
+    xb, dyb = x.to(cuda), dy.to(cuda)
+    ws = torch.zeros(lib.yolo_conv_wgrad_split_workspace_bytes(Cin, Cout, k, DT), dtype=torch.uint8, device=cuda)
+    dw_s = torch.zeros((Cout, Cin, k, k), dtype=torch.float32, device=cuda)
+    dw_b = torch.zeros_like(dw_s)
+    L.check(lib.yolo_conv_wgrad_split(dys.data_ptr(), xs.data_ptr(), dw_s.data_ptr(), N, H, W, Cin, Cout, k, s, 0, 0, DT,
+                                      ws.data_ptr(), 2, _st()), 'wgrad split')
+    L.check(lib.yolo_conv_wgrad_algo(dyb.data_ptr(), xb.data_ptr(), dw_b.data_ptr(), N, H, W, Cin, Cout, k, s, 0, L.BF16,
+                                     ws.data_ptr(), 1, _st()), 'wgrad bf16')
+    torch.cuda.synchronize()
+    assert float(dw_b.abs().max()) > 1.0
+    assert torch.equal(dw_s, dw_b)
+
+
 # ---- data-gradient weight image -----------------------------------------------------------------------------------------
 def _host_dgrad_image(w, Cout_f, Cin_f, k):
     """The split data-gradient image built on the host: rows = forward input channels (padded to 256), K = forward output

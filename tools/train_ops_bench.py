@@ -10,7 +10,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument('--batch', type=int, default=32)
 ap.add_argument('--what', default='bn,wgrad')
 ap.add_argument('--iters', type=int, default=20)
-ap.add_argument('--algos', default='0', help='weight-gradient kernels to time (yolo_conv_wgrad_algo ids)')
+ap.add_argument('--algos', default='0', help='weight-gradient kernels to time (yolo_conv_wgrad_algo ids; bf16x3: yolo_conv_wgrad_split ids 0-2)')
+ap.add_argument('--dtype', default='bf16', choices=['bf16', 'bf16x3'], help='weight gradient: the bf16 entry or the split one')
 ap.add_argument('--k3s1', action='store_true', help='weight gradient: only the 3x3 stride-1 shapes with Cin >= 64')
 ap.add_argument('--k1', action='store_true', help='weight gradient: only the 1x1 shapes')
 ap.add_argument('--s2', action='store_true', help='weight gradient: only the stride-2 shapes')
@@ -77,7 +78,19 @@ WG_SHAPES = [(104, 64, 128, 3, 2), (208, 32, 64, 3, 2), (208, 32, 64, 3, 1), (20
              (13, 2048, 1024, 1, 1), (26, 1024, 512, 1, 1), (52, 512, 256, 1, 1),
              # the deeper stride-2 layers
              (52, 128, 256, 3, 2), (26, 256, 512, 3, 2), (13, 512, 1024, 3, 2)]
+def split_tensor(shape, gen):
+    """Seeded normal values in split storage (..., 2, round_up(C, 32)): hi = bf16(v), lo = bf16(v - hi), pad channels zero."""
+    v = torch.randn(shape, device=dev, generator=gen)
+    C = shape[-1]
+    hi = v.bfloat16()
+    out = torch.zeros(tuple(shape[:-1]) + (2, -(-C // 32) * 32), dtype=torch.bfloat16, device=dev)
+    out[..., 0, :C], out[..., 1, :C] = hi, (v - hi.float()).bfloat16()
+    return out
+
+
 if 'wgrad' in a.what:
+    split = a.dtype == 'bf16x3'
+    gen = torch.Generator(device=dev).manual_seed(0)
     for ho, ci, co, k, s in WG_SHAPES:
         if a.k1 and k != 1:
             continue
@@ -86,15 +99,24 @@ if 'wgrad' in a.what:
         if a.s2 and s != 2:
             continue
         H = ho * s
-        x = torch.randn((a.batch, H, H, ci), device=dev).bfloat16()
-        dy = torch.randn((a.batch, ho, ho, co), device=dev).bfloat16()
+        if split:
+            x, dy = split_tensor((a.batch, H, H, ci), gen), split_tensor((a.batch, ho, ho, co), gen)
+            nws = lib.yolo_conv_wgrad_split_workspace_bytes(ci, co, k, L.BF16X3)
+        else:
+            x = torch.randn((a.batch, H, H, ci), device=dev).bfloat16()
+            dy = torch.randn((a.batch, ho, ho, co), device=dev).bfloat16()
+            nws = lib.yolo_conv_wgrad_workspace_bytes(co, ci, k, 1)
         dw = torch.zeros((co, ci, k, k), device=dev)
-        ws = torch.zeros(max(lib.yolo_conv_wgrad_workspace_bytes(co, ci, k, 1), 16), dtype=torch.uint8, device=dev)
+        ws = torch.zeros(max(nws, 16), dtype=torch.uint8, device=dev)
         fl = 2.0 * a.batch * ho * ho * ci * co * k * k
         for algo in [int(v) for v in a.algos.split(',')]:
-            rc = lib.yolo_conv_wgrad_algo(p(dy), p(x), p(dw), a.batch, H, H, ci, co, k, s, co, 1, p(ws), algo, st)
+            if split:
+                run = lambda: lib.yolo_conv_wgrad_split(p(dy), p(x), p(dw), a.batch, H, H, ci, co, k, s, 0, 0, L.BF16X3, p(ws), algo, st)
+            else:
+                run = lambda: lib.yolo_conv_wgrad_algo(p(dy), p(x), p(dw), a.batch, H, H, ci, co, k, s, co, 1, p(ws), algo, st)
+            rc = run()
             if rc == L.EUNSUPPORTED:
                 continue
             L.check(rc, 'wgrad')
-            t = timed(lambda: L.check(lib.yolo_conv_wgrad_algo(p(dy), p(x), p(dw), a.batch, H, H, ci, co, k, s, co, 1, p(ws), algo, st), "wgrad"))
+            t = timed(lambda: L.check(run(), "wgrad"))
             print('wgrad %3d^2 %4d->%4d k%d s%d algo %d  %7.1f us  %6.1f TFLOP/s' % (ho, ci, co, k, s, algo, t, fl / t / 1e6), flush=True)

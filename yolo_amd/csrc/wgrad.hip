@@ -1,6 +1,7 @@
 // Weight gradient of the convolutions for gfx950 (everything but the row-walk / LDS-DMA kernels of wgrad_walk.hip): the fp32
-// parity kernel (MFMA 32x32x2 f32), the bf16 per-tap / strip / row-group kernels, the split (YOLO_BF16X3) kernel, their
-// launchers and the yolo_conv_wgrad* entry points.
+// parity kernel (MFMA 32x32x2 f32), the bf16 per-tap / strip / row-group kernels, the split (YOLO_BF16X3) per-tap kernel, their
+// launchers (one for both per-tap kernels) and the yolo_conv_wgrad* entry points (bf16: ids -> families, then the ladder strip,
+// row groups, per-tap).
 #include "common.h"
 #include <stdlib.h>
 #include "conv_args.h"
@@ -228,28 +229,6 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(const uint16_t* __restr
         }
 }
 
-template <int MI, int NI>
-static void wgrad_bf16_launch(const uint16_t* dy, const uint16_t* x, float* ws, int N, int H, int W, int Cin, int Ho, int Wo,
-                              int Cout, int ksize, int stride, long long ps, hipStream_t st) {
-    constexpr int BM = MI * 64, BN = NI * 64;
-    const int tiles_ci = (Cin + BN - 1) / BN, tiles_co = (Cout + BM - 1) / BM, taps = ksize * ksize;
-    const long long chunks = ((long long)N * Ho * Wo + WG_KC - 1) / WG_KC;
-    const long long tiles = (long long)tiles_ci * tiles_co * taps;
-    static const long long target_env = YOLO_LAB_ENV("YOLO_PT_TARGET", 0);   // (ablation knob)
-    const long long target = target_env ? target_env : 768;      // the resident capacity: 3 blocks per CU
-    long long slices = target / tiles;                           // rounded DOWN: 774 blocks (one over a full round) cost 212 us where 756 take 185
-    // at least 16 K-chunks per slice: every slice ends with a 128x128 atomic tile, which dominated the small 1x1 layers
-    // (26x26 512->256 at batch 64: 60.7 -> 45.5 us; 8 and 32 chunks are worse)
-    if (slices > chunks / 16) slices = chunks / 16;
-    if (slices > chunks) slices = chunks;
-    if (slices < 1) slices = 1;
-    const int cps = (int)((chunks + slices - 1) / slices);
-    slices = (chunks + cps - 1) / cps;
-    YOLO_LAUNCH((wgrad_bf16_kernel<MI, NI>), dim3((unsigned)(tiles_ci * tiles_co), taps, (unsigned)slices), dim3(256), 0, st,
-                dy, x, ws, N, H, W, Cin, Ho, Wo, Cout, ksize, stride, ps, tiles_ci, cps, slices > 1 ? 1 : 0,
-                make_fastdiv((unsigned)Ho * Wo), make_fastdiv((unsigned)Wo));
-}
-
 // ------------------------------------------------------------------------------------------------
 // SPLIT weight gradient (YOLO_BF16X3): the per-tap kernel above on (hi, lo) pairs.  dy and x each come as two bf16 planes;
 // a K-chunk of SWG_KC pixels stages BOTH planes of both operands in LDS, and every fragment pair issues three MFMAs,
@@ -392,24 +371,39 @@ __global__ __launch_bounds__(256) void wgrad_split_kernel(const uint16_t* __rest
         }
 }
 
-template <int MI, int NI>
-static void wgrad_split_launch(const uint16_t* dy, const uint16_t* x, float* ws, int N, int H, int W, int Cin, int Ho, int Wo,
-                               int Cout, int ksize, int stride, long long dy_ps, int dy_lo, long long x_ps, int x_lo,
-                               bool force_atomic, hipStream_t st) {
-    constexpr int BM = MI * 64, BN = NI * 64;
+// How a launch cuts the pixel range into slices (grid z): about `target` blocks in all, at least `min_chunks` K-chunks per slice
+// because every slice ends in an atomic tile.
+//   bf16: 768 = the resident capacity, 3 blocks per CU, and the quotient is rounded DOWN: 774 blocks (one over a full round) cost
+//     212 us where 756 take 185.  16 chunks: the atomic tiles dominated the small 1x1 layers (26x26 512->256 at batch 64:
+//     60.7 -> 45.5 us; 8 and 32 chunks are worse).
+//   split: about three resident rounds of blocks (1536 of the 64 x 64 tile, else 768); 32 chunks = 1024 pixels.
+struct TapSlices {
+    long long target;
+    int min_chunks;
+};
+
+template <int MI, int NI, int PLANES>
+static void wgrad_tap_launch(const uint16_t* dy, const uint16_t* x, float* ws, int N, int H, int W, int Cin, int Ho, int Wo,
+                             int Cout, int ksize, int stride, long long dy_ps, int dy_lo, long long x_ps, int x_lo,
+                             TapSlices pol, bool force_atomic, hipStream_t st) {
+    constexpr int BM = MI * 64, BN = NI * 64, KC = PLANES == 1 ? WG_KC : SWG_KC;
     const int tiles_ci = (Cin + BN - 1) / BN, tiles_co = (Cout + BM - 1) / BM, taps = ksize * ksize;
-    const long long chunks = ((long long)N * Ho * Wo + SWG_KC - 1) / SWG_KC;
+    const long long chunks = ((long long)N * Ho * Wo + KC - 1) / KC;
     const long long tiles = (long long)tiles_ci * tiles_co * taps;
-    const long long target = MI * NI == 1 ? 1536 : 768;         // about three resident rounds of blocks
-    long long slices = target / tiles;
-    if (slices > chunks / 32) slices = chunks / 32;              // at least 32 chunks (1024 pixels) per slice: each ends in atomics
+    long long slices = pol.target / tiles;
+    if (slices > chunks / pol.min_chunks) slices = chunks / pol.min_chunks;
     if (slices < 1) slices = 1;
     const int cps = (int)((chunks + slices - 1) / slices);
     slices = (chunks + cps - 1) / cps;
-    YOLO_LAUNCH((wgrad_split_kernel<MI, NI>), dim3((unsigned)(tiles_ci * tiles_co), taps, (unsigned)slices), dim3(256), 0, st,
-                dy, x, ws, N, H, W, Cin, Ho, Wo, Cout, ksize, stride, dy_ps, dy_lo, x_ps, x_lo, tiles_ci, cps,
-                (slices > 1 || force_atomic) ? 1 : 0,
-                make_fastdiv((unsigned)Ho * Wo), make_fastdiv((unsigned)Wo));
+    const dim3 grid((unsigned)(tiles_ci * tiles_co), taps, (unsigned)slices);
+    const int use_atomic = (slices > 1 || force_atomic) ? 1 : 0;
+    const FastDiv d_howo = make_fastdiv((unsigned)Ho * Wo), d_wo = make_fastdiv((unsigned)Wo);
+    if constexpr (PLANES == 1)
+        YOLO_LAUNCH((wgrad_bf16_kernel<MI, NI>), grid, dim3(256), 0, st, dy, x, ws, N, H, W, Cin, Ho, Wo, Cout, ksize, stride,
+                    dy_ps, tiles_ci, cps, use_atomic, d_howo, d_wo);
+    else
+        YOLO_LAUNCH((wgrad_split_kernel<MI, NI>), grid, dim3(256), 0, st, dy, x, ws, N, H, W, Cin, Ho, Wo, Cout, ksize, stride,
+                    dy_ps, dy_lo, x_ps, x_lo, tiles_ci, cps, use_atomic, d_howo, d_wo);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -856,6 +850,59 @@ __global__ void wgrad_finish_kernel(float* __restrict__ dwt, float* __restrict__
 // that span `pixels` pixels of the caller's pitch (d_off, d_goff).  They must stay below 2^31 bytes.
 static bool dy_lanes_fit(long long pixels, long long ps) { return ps <= (0x7fffffffLL - 4096) / (2 * pixels); }
 
+// the finishing launch behind every kernel that accumulates into the [tap][Cout][Cin] workspace
+static int wgrad_finish(float* ws, float* dw_oihw, int Cout, int Cin, int taps, hipStream_t st) {
+    const long long total = (long long)Cin * Cout * taps;
+    YOLO_LAUNCH(wgrad_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ws, dw_oihw, Cout, Cin, taps, total);
+    YOLO_LAUNCH_CHECK();
+    return YOLO_OK;
+}
+
+// The register-staged bf16 families as yolo_conv_wgrad_algo tries them, in this order: each launches into the workspace and
+// returns YOLO_OK, or YOLO_EUNSUPPORTED for a shape outside its domain or past its offset limits.
+struct WgradShape {
+    const uint16_t* dy;
+    const uint16_t* x;
+    float* ws;
+    int N, H, W, Cin, Ho, Wo, Cout, ksize, stride;
+    long long ps;
+    hipStream_t st;
+};
+
+// strip kernel: 3x3, Cin <= 64
+// (the 64 -> 128 stride-2 layer: the per-tap kernel measures 388 us against the strip kernel's 503 at 208^2 bs 64)
+// (x: 64-bit bases per step, so any extent; dy: the lane offsets span TH rows of a 32-pixel strip -- a pitch too wide for that
+//  goes on to the per-tap kernel, and so does a row so wide that the `int x_off` of the two staged rows would pass 2^31 bytes:
+//  millions of columns)
+static int wgrad_strip_try(const WgradShape& g) {
+    if (!(g.ksize == 3 && g.Cin <= 64 && !(g.stride == 2 && g.Cin == 64) && dy_lanes_fit((g.stride == 2 ? 0LL : g.Wo) + 32, g.ps) &&
+          (2LL * g.W + 128) * g.Cin * 2 < 0x7fffffffLL))
+        return YOLO_EUNSUPPORTED;
+    // CO_F = 1 (144 accumulator registers): CO_F = 2 needs 288 and spills
+    if (g.stride == 2) wgrad_strip_launch<1, 2, 1>(g.dy, g.x, g.ws, g.N, g.H, g.W, g.Cin, g.Ho, g.Wo, g.Cout, g.ps, g.st);
+    else wgrad_strip_launch<1, 1, 2>(g.dy, g.x, g.ws, g.N, g.H, g.W, g.Cin, g.Ho, g.Wo, g.Cout, g.ps, g.st);
+    return YOLO_OK;
+}
+
+// row-group kernel: wins on the narrow deep maps (26x26: 210 -> 163 us, 13x13: 211 -> 175 us at batch 64); on wider
+// maps its atomic epilogue (one 64x64x9 tile per block) costs more than the saved L2 traffic
+// (x: a 64-bit base per row group, so any extent; dy: the lane offsets span a group of at most 7 * 16 pixels -- as above)
+static int wgrad_rows_try(const WgradShape& g) {
+    if (!(g.ksize == 3 && g.stride == 1 && g.W <= 40 && dy_lanes_fit(112, g.ps))) return YOLO_EUNSUPPORTED;
+    return wgrad_rows_dispatch(g.dy, g.x, g.ws, g.N, g.H, g.W, g.Cin, g.Cout, g.ps, g.st) ? YOLO_OK : YOLO_EUNSUPPORTED;
+}
+
+// per-tap kernel, 128 x 128 tiles (256x128 / 128x256 / 256x256 tiles were measured 10-40 % slower: one wave per SIMD)
+static int wgrad_tap_try(const WgradShape& g) {
+    if ((long long)g.N * g.H * g.W * g.Cin * 2 >= 0xffffff00LL || (long long)g.N * g.Ho * g.Wo >= 0x7fffffffLL)
+        return YOLO_EUNSUPPORTED;                            // (32-bit buffer offsets into x)
+    if (!dy_lanes_fit(WG_KC, g.ps)) return YOLO_EUNSUPPORTED;    // (dy: the lane offsets span one K-chunk)
+    static const long long target_env = YOLO_LAB_ENV("YOLO_PT_TARGET", 0);   // (ablation knob)
+    wgrad_tap_launch<2, 2, 1>(g.dy, g.x, g.ws, g.N, g.H, g.W, g.Cin, g.Ho, g.Wo, g.Cout, g.ksize, g.stride, g.ps, 0, g.Cin, 0,
+                              TapSlices{target_env ? target_env : 768, 16}, false, g.st);
+    return YOLO_OK;
+}
+
 extern "C" long long yolo_conv_wgrad_workspace_bytes(int Cin, int Cout, int ksize, int dtype) {
     if (Cin <= 0 || Cout <= 0 || (ksize != 1 && ksize != 3) || (dtype != YOLO_BF16 && dtype != YOLO_F32)) return YOLO_EINVAL;
     if (dtype != YOLO_BF16) return 0;
@@ -889,66 +936,23 @@ extern "C" int yolo_conv_wgrad_algo(const void* dy, const void* x, float* dw_oih
     if ((long long)N * H * W >= 0x7fffffffLL) return YOLO_EUNSUPPORTED;
     const int pad = ksize / 2;
     const int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
-    const int taps = ksize * ksize;
     hipStream_t st = (hipStream_t)stream;
     (void)hipGetLastError();
-    const long long total = (long long)Cin * Cout * taps;
-    if ((algo == 0 || algo == 5 || algo == 6) && ksize == 1) {
-        // (adds straight into dw_oihw: [cout][cin] is the OIHW layout of a 1x1)
-        const int rc = wgrad_gemm_dispatch(dy, x, dw_oihw, (long long)N * H * W, Cin, Cout, ps, algo ? algo - 4 : 0, st);
-        if (rc != YOLO_EUNSUPPORTED || algo) return rc;
-    } else if (algo >= 5) {
-        return YOLO_EUNSUPPORTED;
-    }
-    if (algo != 1 && ksize == 3 && stride == 1) {
-        // (adds straight into dw_oihw: no workspace, no finishing pass)
-        const int rc = wgrad_walk_dispatch(dy, x, dw_oihw, N, H, W, Cin, Cout, ps, algo ? algo - 1 : 0, st);
-        if (rc != YOLO_EUNSUPPORTED || algo) return rc;
-    } else if (algo > 1 && algo < 5) {
-        return YOLO_EUNSUPPORTED;
-    }
-    // (the 64 -> 128 stride-2 layer: the per-tap kernel measures 388 us against the strip kernel's 503 at 208^2 bs 64)
-    // (x: 64-bit bases per step, so any extent; dy: the lane offsets span TH rows of a 32-pixel strip -- a pitch too wide for that
-    //  goes on to the per-tap kernel, and so does a row so wide that the `int x_off` of the two staged rows would pass 2^31 bytes:
-    //  millions of columns)
-    if (ksize == 3 && Cin <= 64 && !(stride == 2 && Cin == 64) && dy_lanes_fit((stride == 2 ? 0LL : Wo) + 32, ps) &&
-        (2LL * W + 128) * Cin * 2 < 0x7fffffffLL) {
-        const uint16_t* d16 = (const uint16_t*)dy;
-        const uint16_t* x16 = (const uint16_t*)x;
-        float* ws = (float*)workspace;
-        // CO_F = 1 (144 accumulator registers): CO_F = 2 needs 288 and spills
-        if (stride == 2) wgrad_strip_launch<1, 2, 1>(d16, x16, ws, N, H, W, Cin, Ho, Wo, Cout, ps, st);
-        else wgrad_strip_launch<1, 1, 2>(d16, x16, ws, N, H, W, Cin, Ho, Wo, Cout, ps, st);
-        YOLO_LAUNCH(wgrad_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (float*)workspace,
-                    dw_oihw, Cout, Cin, taps, total);
-        YOLO_LAUNCH_CHECK();
-        return YOLO_OK;
-    }
-    // row-group kernel: wins on the narrow deep maps (26x26: 210 -> 163 us, 13x13: 211 -> 175 us at batch 64); on wider
-    // maps its atomic epilogue (one 64x64x9 tile per block) costs more than the saved L2 traffic
-    // (x: a 64-bit base per row group, so any extent; dy: the lane offsets span a group of at most 7 * 16 pixels -- as above)
-    if (ksize == 3 && stride == 1 && W <= 40 && dy_lanes_fit(112, ps)) {
-        if (wgrad_rows_dispatch((const uint16_t*)dy, (const uint16_t*)x, (float*)workspace, N, H, W, Cin, Cout, ps, st)) {
-            YOLO_LAUNCH(wgrad_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                        (float*)workspace, dw_oihw, Cout, Cin, taps, total);
-            YOLO_LAUNCH_CHECK();
-            return YOLO_OK;
-        }
-    }
-    {
-        const uint16_t* d16 = (const uint16_t*)dy;
-        const uint16_t* x16 = (const uint16_t*)x;
-        float* ws = (float*)workspace;
-        // (256x128 / 128x256 / 256x256 tiles were measured 10-40 % slower: one wave per SIMD)
-        if ((long long)N * H * W * Cin * 2 >= 0xffffff00LL || (long long)N * Ho * Wo >= 0x7fffffffLL)
-            return YOLO_EUNSUPPORTED;                        // (32-bit buffer offsets into x)
-        if (!dy_lanes_fit(WG_KC, ps)) return YOLO_EUNSUPPORTED;  // (dy: the lane offsets span one K-chunk)
-        wgrad_bf16_launch<2, 2>(d16, x16, ws, N, H, W, Cin, Ho, Wo, Cout, ksize, stride, ps, st);
-    }
-    YOLO_LAUNCH(wgrad_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (float*)workspace,
-                dw_oihw, Cout, Cin, taps, total);
-    YOLO_LAUNCH_CHECK();
-    return YOLO_OK;
+    const bool k1 = ksize == 1, k3s1 = ksize == 3 && stride == 1;
+    // a kernel named by its id: its status is final.  (Both add straight into dw_oihw -- [cout][cin] is the OIHW layout of a
+    // 1x1 -- with no workspace and no finishing pass.)
+    if (algo >= 5) return k1 ? wgrad_gemm_dispatch(dy, x, dw_oihw, (long long)N * H * W, Cin, Cout, ps, algo - 4, st) : YOLO_EUNSUPPORTED;
+    if (algo >= 2) return k3s1 ? wgrad_walk_dispatch(dy, x, dw_oihw, N, H, W, Cin, Cout, ps, algo - 1, st) : YOLO_EUNSUPPORTED;
+    // the library's choice: the GEMM / the row walk where they take the shape, ahead of the register-staged kernels
+    int rc = YOLO_EUNSUPPORTED;
+    if (algo == 0 && k1) rc = wgrad_gemm_dispatch(dy, x, dw_oihw, (long long)N * H * W, Cin, Cout, ps, 0, st);
+    if (algo == 0 && k3s1) rc = wgrad_walk_dispatch(dy, x, dw_oihw, N, H, W, Cin, Cout, ps, 0, st);
+    if (rc != YOLO_EUNSUPPORTED) return rc;
+    const WgradShape g = {(const uint16_t*)dy, (const uint16_t*)x, (float*)workspace, N, H, W, Cin, Ho, Wo, Cout, ksize, stride, ps, st};
+    rc = wgrad_strip_try(g);
+    if (rc == YOLO_EUNSUPPORTED) rc = wgrad_rows_try(g);
+    if (rc == YOLO_EUNSUPPORTED) rc = wgrad_tap_try(g);
+    return rc == YOLO_OK ? wgrad_finish(g.ws, dw_oihw, Cout, Cin, ksize * ksize, st) : rc;
 }
 
 // Split weight gradient (YOLO_BF16X3).  algo 0 = the library's choice, 1 = 64 x 64 tiles, 2 = 128 x 128 tiles.
@@ -983,8 +987,6 @@ extern "C" int yolo_conv_wgrad_split(const void* dy, const void* x, float* dw_oi
     if (!dy_lanes_fit(SWG_KC + 1, ps)) return YOLO_EUNSUPPORTED;                // (dy: a K-chunk of pixels and the lo plane behind the last)
     hipStream_t st = (hipStream_t)stream;
     (void)hipGetLastError();
-    const int taps = ksize * ksize;
-    const long long total = (long long)Cin * Cout * taps;
     const int variant = algo ? algo : ((Cin <= 64 || Cout <= 64) ? 1 : 2);
     const bool sliced = per < N;
     for (long long n0 = 0; n0 < N; n0 += per) {
@@ -992,14 +994,11 @@ extern "C" int yolo_conv_wgrad_split(const void* dy, const void* x, float* dw_oi
         const uint16_t* d16 = (const uint16_t*)dy + n0 * Ho * Wo * ps;
         const uint16_t* x16 = (const uint16_t*)x + n0 * H * W * x_ps;
         if (variant == 1)
-            wgrad_split_launch<1, 1>(d16, x16, (float*)workspace, n, H, W, Cin, Ho, Wo, Cout, ksize, stride, ps, (int)lo, x_ps, x_lo,
-                                     sliced, st);
+            wgrad_tap_launch<1, 1, 2>(d16, x16, (float*)workspace, n, H, W, Cin, Ho, Wo, Cout, ksize, stride, ps, (int)lo, x_ps, x_lo,
+                                      TapSlices{1536, 32}, sliced, st);
         else
-            wgrad_split_launch<2, 2>(d16, x16, (float*)workspace, n, H, W, Cin, Ho, Wo, Cout, ksize, stride, ps, (int)lo, x_ps, x_lo,
-                                     sliced, st);
+            wgrad_tap_launch<2, 2, 2>(d16, x16, (float*)workspace, n, H, W, Cin, Ho, Wo, Cout, ksize, stride, ps, (int)lo, x_ps, x_lo,
+                                      TapSlices{768, 32}, sliced, st);
     }
-    YOLO_LAUNCH(wgrad_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (float*)workspace, dw_oihw,
-                Cout, Cin, taps, total);
-    YOLO_LAUNCH_CHECK();
-    return YOLO_OK;
+    return wgrad_finish((float*)workspace, dw_oihw, Cout, Cin, ksize * ksize, st);
 }
